@@ -1,7 +1,7 @@
 """Benchmark: defended utterances/s of the AdaIN-VC embedding attack
 (n_iters=1500, eps=0.1) on MI355X — BASELINE.json `metric`, configs[1] workload
 (B=256 utterances of 80x128 normalized mel per GPU, bf16 MFMA operands with fp32
-accumulation / Adam state; the fp32 path is timed too and reported beside it).
+accumulation / Adam state; --full times the fp32 path too and reports it beside it).
 --attack e2e / fb measure configs[2] / [3] (end-to-end and feedback attacks); --attack pm
 measures configs[4] (VSMask PredictiveModel forward, windows/s of [B,1,80,100]);
 --attack mel2wav measures the back end after the attack: denormalize +
@@ -17,7 +17,11 @@ loudly when fewer than N GPUs are visible -- never a silent 1-GPU run).  --dry-r
 exercises that launcher, the rendezvous (gloo), sharding, timing and the JSON line on
 the CPU without computing an attack (the multi-rank CPU test drives it).
 
-Also reported:
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints the JSON line (ms_per_step = one timed step).
+
+With --full also measured, after the timed region (null in the line otherwise):
+  fp32          one warm-up and one timed step of the exact-fp32 path on the same workload.
   roofline      dominant kernel's algorithmic FLOP / its average launch time
                 (HIP events on libavc's stream, a separate profiled pass after
                 the timed region) vs the gfx950 dense peak for the dtype.
@@ -90,7 +94,39 @@ def parse():
                     help="--lengths: per-length buckets (attack_many's default) instead of the ragged batch, for comparison")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only: launcher + gloo rendezvous + sharding + timing, no attack computed")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the fp32 comparison "
+                         "step, the roofline passes (in-graph kernel timing, HIP-event profile), the CPU baselines "
+                         "and mel2wav's front-end timing (each can still be switched off with its --no-* flag); "
+                         "without --full the line reports them as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "at most 64 MB in all, a fixed seeded sample of a larger output); inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_fp32_compare = a.no_cpu_baseline = a.no_roofline = True
+    return a
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(a, arrays, rank=0, world=1):
+    """--dump-outputs DIR: the tensors the timed path returned in its last step, as DIR/<name>.npy in float32
+    (<name>.rank<r>.npy per rank at N > 1).  The 64 MB cap is shared evenly by the arrays and ranks; an array
+    over its share is stored as a fixed sample of its flattened elements (seed 0, sorted indices)."""
+    if not a.dump_outputs:
+        return
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    share = DUMP_MAX_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        x = t.detach().to(torch.float32).cpu().numpy()
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // 4, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(a.dump_outputs, name + ("" if world == 1 else f".rank{rank}") + ".npy"), x)
 
 
 KFD_NODES = "/sys/class/kfd/kfd/topology/nodes"
@@ -327,8 +363,8 @@ def main_pm(a):
     total = B * world
     x_all = torch.randn(total, 1, 80, 100, generator=torch.Generator().manual_seed(1))
     x = x_all[shard.shard_slice(total, rank, world)].contiguous().to(dev)
-    steps = max(a.steps, 20)                 # a step is ~ms: time at least 20 of them
-    for _ in range(max(a.warmup, 3)):
+    steps = a.steps                          # a step is ~ms: ask for 20 or more of them
+    for _ in range(a.warmup):
         md(x)
     torch.cuda.synchronize()
     if dist:
@@ -341,6 +377,7 @@ def main_pm(a):
         dist.barrier()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist, None)
     assert torch.isfinite(y).all()
+    dump_outputs(a, {"y": y}, rank, world)
     cpu = cpu_baseline_pm(min(a.cpu_seconds, 10.0), sd) if rank == 0 and world == 1 and not a.no_cpu_baseline else None
     if rank == 0:
         value = total * steps / elapsed
@@ -426,6 +463,7 @@ def main_mel2wav(a):
         dist.barrier()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist, None)
     assert torch.isfinite(out).all()
+    dump_outputs(a, {"wav": out}, rank, world)
     roof = None
     if not a.no_roofline:
         d.set_profiling(True)
@@ -454,21 +492,24 @@ def main_mel2wav(a):
                 roof["traffic"] = tr
     # front end on the same shapes: B trimmed waveforms of hop * (T - 1) samples -> normalized
     # [B, 80, T] mels (file2mel after load / trim + normalize, one dsp_wav2mel launch)
-    wav = out.contiguous()
-    for _ in range(3):
-        d.wav2mel(wav, attr["mean"], attr["std"], True)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        mel_fe = d.wav2mel(wav, attr["mean"], attr["std"], True)
-    e1.record()
-    torch.cuda.synchronize()
-    fe_ms = e0.elapsed_time(e1) / 20
-    assert mel_fe.shape == (B, 80, T) and torch.isfinite(mel_fe).all()
-    fe_bytes = B * (wav.shape[1] + 80 * T) * 4          # algorithmic: read the waveform, write the mel
-    front = {"kernel": "dsp_wav2mel", "utts_per_s": round(B / (fe_ms * 1e-3), 1), "avg_launch_ms": round(fe_ms, 4),
-             "bytes_per_launch": fe_bytes, "hbm_frac": round(fe_bytes / (fe_ms * 1e-3) / 1e9 / HBM_PEAK, 4)}
+    front = None
+    if a.full:
+        wav = out.contiguous()
+        for _ in range(3):
+            d.wav2mel(wav, attr["mean"], attr["std"], True)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            mel_fe = d.wav2mel(wav, attr["mean"], attr["std"], True)
+        e1.record()
+        torch.cuda.synchronize()
+        fe_ms = e0.elapsed_time(e1) / 20
+        assert mel_fe.shape == (B, 80, T) and torch.isfinite(mel_fe).all()
+        fe_bytes = B * (wav.shape[1] + 80 * T) * 4          # algorithmic: read the waveform, write the mel
+        front = {"kernel": "dsp_wav2mel", "utts_per_s": round(B / (fe_ms * 1e-3), 1),
+                 "avg_launch_ms": round(fe_ms, 4), "bytes_per_launch": fe_bytes,
+                 "hbm_frac": round(fe_bytes / (fe_ms * 1e-3) / 1e9 / HBM_PEAK, 4)}
     cpu = None
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         import numpy as np
@@ -585,6 +626,8 @@ def main_lengths(a):
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist, None)
     hb_stop.set()
     assert all(torch.isfinite(o).all() for o in out)
+    # the defended utterances [80, t_i] side by side along the frame axis, in input order
+    dump_outputs(a, {"adv": torch.cat([o.reshape(80, -1) for o in out], dim=1)}, rank, world)
     frames = sum(lens_all)
     roof = None
     if not a.no_roofline:
@@ -713,6 +756,7 @@ def main():
     torch.cuda.synchronize()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dist, None)
     assert torch.isfinite(out).all()
+    dump_outputs(a, {"adv": out}, rank, world)
 
     fp32_cmp = None
     if a.precision != "fp32" and not a.no_fp32_compare:

@@ -23,6 +23,8 @@ if [ "${SMOKE:-1}" = "1" ]; then
 fi
 
 if [ "${BENCH:-1}" = "1" ]; then
+  # the default line carries the fp32 comparison, roofline and CPU baselines: bench.py --full
+  : "${BENCH_ARGS=--full}"
   timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; tail -1 gpurun_out/bench.log
   [ $rc -eq 0 ] || { tail -20 gpurun_out/bench.log; stop bench $rc; }

@@ -112,6 +112,51 @@ def test_bench_launcher_dry_run(world, batch):
     assert out["shard_sizes"] == [batch] * world
 
 
+def test_bench_plain_run_measures_only_the_headline(monkeypatch):
+    """Without --full the fp32 comparison, the roofline passes and the CPU baselines are off; --full leaves
+    them on, each still switchable by its own flag."""
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    assert a.no_fp32_compare and a.no_roofline and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-roofline"])
+    a = bench.parse()
+    assert a.full and a.no_roofline and not a.no_fp32_compare and not a.no_cpu_baseline
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array; over the size cap, the same seeded sample every time."""
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class A:
+        dump_outputs = None
+    x = torch.randn(3, 80, 16, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
+    bench.dump_outputs(A(), {"adv": x})                       # option not given: nothing written
+    assert list(tmp_path.iterdir()) == []
+    A.dump_outputs = str(tmp_path / "o")
+    bench.dump_outputs(A(), {"adv": x})
+    got = np.load(tmp_path / "o" / "adv.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    bench.dump_outputs(A(), {"adv": x}, rank=1, world=2)
+    assert np.array_equal(np.load(tmp_path / "o" / "adv.rank1.npy"), got)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 400)      # two arrays: 100 float32 elements each
+    y = x * 2
+    bench.dump_outputs(A(), {"adv": x, "other": y})
+    s, t = np.load(tmp_path / "o" / "adv.npy"), np.load(tmp_path / "o" / "other.npy")
+    assert s.shape == t.shape == (100,) and s.dtype == np.float32
+    assert np.array_equal(t, s * 2)                            # the same elements of both arrays
+    assert np.isin(s, got).all() and len(np.unique(s)) == 100
+    bench.dump_outputs(A(), {"adv": x, "other": y})
+    assert np.array_equal(np.load(tmp_path / "o" / "adv.npy"), s)
+
+
 def test_bench_refuses_missing_gpus():
     """No silent single-GPU number: --gpus 2 with fewer visible GPUs (none here) fails loudly."""
     r = _bench("--gpus", "2", "--steps", "1", timeout=120)
