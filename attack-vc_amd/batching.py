@@ -21,14 +21,17 @@ result equals attack_utils.*_attack on utterance i alone, bit for bit.
 
 ragged=True (emb attack): instead of one batch per length, ONE ragged batch per chunk of up to
 max_batch utterances of ANY lengths (avc_emb_attack_ragged: every SpeakerEncoder pass is one launch,
-each workgroup its own utterance length, on the long engine), longest first so that neighbouring
-workgroups -- dealt round-robin over the 8 XCDs -- carry similar work.  With real data's spread of
-lengths the per-length buckets are mostly of one or two utterances (a handful of the 256 CUs busy);
-the ragged batch keeps every CU busy.  Utterance i then equals its single-utterance attack on the long
-engine (AVC_ENGINE_LONG) bit for bit -- the fused engine's result too in fp32, where the two engines
-are bitwise equal (tests/test_gpu_long.py).  libavc caches one
-workspace (buffers, plans, captured graphs) per shape, and attack_many sizes that cache to the
-shapes it uses, so a second call over the same lengths re-plans nothing (avc_ws_stats).
+each workgroup its own utterance length), longest first so that neighbouring workgroups -- dealt
+round-robin over the 8 XCDs -- carry similar work.  With real data's spread of lengths the per-length
+buckets are mostly of one or two utterances (a handful of the 256 CUs busy); the ragged batch keeps
+every CU busy.  The engine is chosen per chunk: the fused runtime-length kernels when every length of
+the chunk is in (64, 128] (and the engine is not forced to long), otherwise the long engine.  Utterance i
+equals its single-utterance attack on that chunk's engine bit for bit: on the long engine
+(AVC_ENGINE_LONG) for a long-engine chunk, attack_utils.emb_attack's under AUTO for a fused chunk of
+lengths below 128 (the same runtime-length kernels).  In fp32 the two engines are bitwise equal
+(tests/test_gpu_long.py), so there every utterance equals attack_utils.emb_attack's result.  libavc
+caches one workspace (buffers, plans, captured graphs) per shape and engine, and attack_many sizes that
+cache to the shapes it uses, so a second call over the same lengths re-plans nothing (avc_ws_stats).
 """
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple

@@ -13,12 +13,15 @@
 #include <deque>
 #include <list>
 #include <map>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/avc.h"
 #include "avc_kernels.h"
 #include "avc_ktime.h"
+#include "avc_lru.h"
 
 namespace avc {
 template <int PREC, int WM, int WN, int WGM, int WGN, int KC, int MODE, int STRIDE>
@@ -95,11 +98,80 @@ static int fail(const char* fmt, ...) {
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 static inline int cdiv(int x, int m) { return (x + m - 1) / m; }
 
+// Environment switches, all read through env_is / env_int (the tune-file path aside).  A/B and
+// diagnostic knobs; read where they act, so a process may flip one between calls unless noted.
+//   AVC_FUSED=0           AUTO engine: the layered engine instead of fused / long (default fused)
+//   AVC_LONG=1            the long engine at every length (default: above 128 frames)
+//   AVC_FUSED_STD=0       no compile-time-shape kernels for the standard config (default on)
+//   AVC_FUSED_RT=0        no runtime-length kernels at 64 < T < 128 (default on)
+//   AVC_FUSED_RT_FORCE=1  the runtime-length kernels at T = 128 too (default off)
+//   AVC_RAGGED_FUSED=0    ragged batches with every length in (64,128]: the long engine (default fused)
+//   AVC_FUSE_HEAD=0       separate se_head_v launches instead of the head in the encoder kernels' tail
+//   AVC_PERSIST=0         bf16 emb attack: per-pass launches instead of the persistent kernel
+//   AVC_PERSIST16=0       ... for the runtime-length shape only
+//   AVC_NO_GRAPH=1        plain launches instead of graph replay
+//   AVC_KSPLIT=n          layered engine: split-K factor of every eligible GEMM (default by shape)
+//   AVC_AUTOTUNE=0        layered engine: keep the default tile variants
+//   AVC_TUNE_FILE=path    layered engine: read / append tuned tile choices
+//   AVC_WS_CACHE=n        workspace cache entries, over avc_set_ws_cache (default 6)
+//   AVC_PRINT_PLAN        (set) one stderr line per launch of a tuned plan
+//   AVC_PROFILE_ROLES     (set) per-layer rows in the profile
+//   AVC_DEBUG_WS=1        trace workspace cache lookups / evictions (read once per process)
+//   AVC_DEBUG_SYNC=1      synchronise after every launch (read once per process)
+//   AVC_PM_MFMA=0         PredictiveModel: every layer on pm_conv (default matrix-core kernels)
+//   AVC_PM_MT=2           PredictiveModel: 32-row tiles on the wide layers (default 64)
+//   AVC_PM_NT=1|2|4       PredictiveModel: N tiles per wave (default 1 at MT = 4, else 2)
+//   AVC_PM_KSWG=n         PredictiveModel: split-K workgroup target of pm_mfma (default 256)
+//   AVC_PM_EDGE=0         PredictiveModel: the Cin = 1 / Cout = 1 layers on pm_conv
+//   AVC_PM_COUT1H=0       PredictiveModel: no half-channel kernel for the Cout = 1 layer
+// env_is(name, c): the variable is set and starts with c (c = 0: set at all).
+static bool env_is(const char* name, char c) {
+    const char* e = getenv(name);
+    return e && (!c || e[0] == c);
+}
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// AVC_DEBUG_WS=1, read once per process: both workspace caches trace their lookups
+static bool debug_ws() {
+    static const bool on = env_is("AVC_DEBUG_WS", '1');
+    return on;
+}
+
 namespace {
 
+// Owners of device memory and graphs: move-only, released by their destructors.  Every path that
+// destroys one (eviction, failed build, avc_destroy) has the owner's device current and its stream
+// drained.  Launch and the kernels' *Args hold plain pointers into them.
+struct DevFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+struct PinnedFree {
+    void operator()(void* p) const { (void)hipHostFree(p); }
+};
+struct GraphFree {
+    void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); }
+};
+template <class T>
+using DevPtr = std::unique_ptr<T, DevFree>;
+using GraphExec = std::unique_ptr<std::remove_pointer<hipGraphExec_t>::type, GraphFree>;
+
+// grow-only float buffer (dalloc)
 struct DevBuf {
     float* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
 };
 
 // A conv layer of the SpeakerEncoder as stored by torch: W[co][ci][k], b[co].
@@ -158,8 +230,24 @@ struct Launch {
 
 struct Plan {
     std::vector<Launch> launches;
-    std::vector<Problem*> owned;
+    std::vector<DevPtr<Problem>> owned;   // the launches' device problem tables
 };
+
+// long-engine scratch: the kernels' view `a` and the three blocks it points into
+struct LongScratch {
+    LongArgs a{};
+    DevPtr<char> img;
+    DevPtr<float> fl;
+    DevPtr<unsigned long long> masks;
+};
+
+// Destroy x's value in reverse member order -- a struct of plans and graphs declares the graphs
+// last, so they go before the tables they reference -- and leave a fresh one.
+template <class T>
+static void renew(T& x) {
+    { T old = std::move(x); }
+    x = T{};
+}
 
 struct Workspace {
     int B = 0, T = 0;
@@ -169,33 +257,33 @@ struct Workspace {
     DevBuf losses, table, scal, slab;
     DevBuf pooled, gpooled;           // fused path: [B][128] time-mean of h_N and its gradient
     DevBuf loss_cur;                  // fused head: [B] per-utterance loss of the current iteration
-    unsigned long long* masks = nullptr;   // fused path: ReLU' ballot words [B][mask_words]
+    DevPtr<unsigned long long> masks; // fused path: ReLU' ballot words [B][mask_words]
     int mask_words = 0;
     bool fused = false;               // this (B, T) runs on the fused family (fused or long engine)
     bool lz = false;                  // ... on the long engine (T > 128, or forced)
-    LongArgs lza{};                   // long engine: scratch (images, fp32 streams, ballot masks)
+    LongScratch lzs;                  // long engine: scratch (images, fp32 streams, ballot masks)
     int iters_cap = 0;
-    int* step = nullptr;
-    Plan fwd, iter, iter_bf16;
-    hipGraphExec_t graph = nullptr, graph_bf16 = nullptr;
-    Plan hdr_it[2];                   // header optimiser iteration [prec]
-    hipGraphExec_t hdr_graph[2] = {nullptr, nullptr};
+    DevPtr<int> step;
     DevBuf hdr, hdr_m, hdr_v, hdr_gx; // header [F*T], its Adam state, d loss / d x [N][F*T]
-    bool built = false;
     int gen = 0;                      // ctx-unique id of this workspace's current plans (set on every (re)plan)
-    // ragged batch (avc_emb_attack_ragged): utterance b has lens[b] frames; inputs / Adam state are packed
-    // [80][lens[b]] blocks; long engine, scratch sized for T = the longest
+    // ragged batch (avc_emb_attack_ragged): utterance b has lens[b] frames (the cache key's); inputs / Adam
+    // state are packed [80][lens[b]] blocks; scratch sized for T = the longest (fused: the 128-frame bound)
     bool ragged = false;
-    std::vector<int> lens;
-    RagUtt* rag = nullptr;            // device [B]: lengths, per-block lengths, packed offsets
+    DevPtr<RagUtt> rag;               // device [B]: lengths, per-block lengths, packed offsets
     double flop_fwd = 0;              // algorithmic FLOPs of one SpeakerEncoder pass over the batch
     size_t X = 0;                     // floats of one input / state array (B x 80 x T, or the packed sum)
+    struct Plans {                    // rebuilt whenever the tables grow (renew)
+        Plan fwd, iter, iter_bf16;
+        Plan hdr_it[2];               // header optimiser iteration [prec]
+        GraphExec graph, graph_bf16, hdr_graph[2];
+    } pl;                             // last: destroyed before the buffers its launches point into
 };
 
 }  // namespace
 
 struct VcState;   // ContentEncoder + Decoder of the e2e / fb attacks (avc_vc_host.inc)
 static void vc_free(avc_ctx* ctx);
+static long vc_evictions(avc_ctx* ctx);   // evictions of the attached VC cache
 
 struct avc_ctx {
     VcState* vc = nullptr;
@@ -219,24 +307,24 @@ struct avc_ctx {
     int engine = AVC_ENGINE_AUTO;       // avc_set_engine
     std::deque<DevBuf> fz_bufs;         // packed fused-engine A operands (both precisions)
     FusedW fzw[2];                      // [PREC_F32], [PREC_BF16]
-    std::map<const float*, void*> bf16_of;   // fp32 A matrix -> its bf16 copy (device)
+    std::map<const float*, DevPtr<void>> bf16_of;   // fp32 A matrix -> its bf16 copy (device)
     hipStream_t stream = nullptr;
     hipEvent_t ev_user = nullptr, ev_done = nullptr;
     // per-call constants (Adam table, scalars) go through this persistent pinned buffer:
     // the copies stay asynchronous, and a later call only waits for them (ev_stage), never
     // for the caller's queued work
-    float* stage = nullptr;
+    std::unique_ptr<float, PinnedFree> stage;
     size_t stage_n = 0;
     hipEvent_t ev_stage = nullptr;
-    // Workspaces cached by shape: (B, T, engine) -> buffers + plans + captured graphs, most
-    // recently used first.  A call at a shape seen before re-plans nothing (real data: a stream of
+    // Workspaces cached by SeKey {B, T, engine, lens} -> buffers + plans + captured graphs, most
+    // recently used first.  A call at a key seen before re-plans nothing (real data: a stream of
     // mixed-length utterances, and an adv_tgt embedded at its own length before the attack);
-    // the least recently used entry is freed past ws_cap entries.
-    std::list<Workspace> wss;
+    // the least recently used entry is freed past wss.cap entries.
+    LruCache<SeKey, Workspace> wss;
     Workspace* cur = nullptr;           // the workspace of the call in progress
-    int ws_cap = 6;
     int gen_next = 0;                   // source of Workspace::gen (unique over the ctx's life)
-    long n_ws_builds = 0, n_ws_replans = 0, n_ws_hits = 0, n_graph_captures = 0, n_ws_evictions = 0;
+    long n_ws_builds = 0, n_ws_replans = 0, n_ws_hits = 0, n_graph_captures = 0;
+    long n_vc_evictions = 0;            // evictions of VC caches already detached (vc_free)
     bool profiling = false;
     std::map<std::string, std::pair<double, double>> prof;   // name -> (total ms, total flop)
     std::map<std::string, long> prof_n;
@@ -247,19 +335,20 @@ struct avc_ctx {
 
 static int dalloc(DevBuf& b, size_t n) {
     if (b.n >= n && b.p) return 0;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
+    b = DevBuf{};
     if (n == 0) return 0;
     HIPCHK(hipMalloc(&b.p, n * sizeof(float)));
     b.n = n;
     return 0;
 }
 
-static void dfree(DevBuf& b) {
-    if (b.p) hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
+// a raw device block of `bytes` into its owner
+template <class T>
+static int dmalloc(DevPtr<T>& d, size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    d.reset(static_cast<T*>(p));
+    return 0;
 }
 
 // The packers build A^T as [K][Mpad]; the kernels read A row-major [Mpad][Kld]
@@ -302,10 +391,9 @@ static int upload_A(avc_ctx* ctx, DevBuf& b, const std::vector<float>& h) {
     if (upload(b, h)) return 1;
     std::vector<uint16_t> hb(h.size());
     for (size_t i = 0; i < h.size(); ++i) hb[i] = to_bf16(h[i]);
-    void* d = nullptr;
-    HIPCHK(hipMalloc(&d, hb.size() * 2));
-    HIPCHK(hipMemcpy(d, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-    ctx->bf16_of[b.p] = d;
+    DevPtr<void>& d = ctx->bf16_of[b.p];
+    if (dmalloc(d, hb.size() * 2)) return 1;
+    HIPCHK(hipMemcpy(d.get(), hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -518,6 +606,8 @@ extern "C" int avc_create(int device, const avc_se_cfg* cfgp, const float* w, si
     avc_ctx* ctx = new avc_ctx();
     ctx->device = device;
     ctx->cfg = c;
+    ctx->wss.tag = "ws";
+    ctx->wss.trace = debug_ws();
     for (int k = c.bank_scale; k <= c.bank_size; k += c.bank_scale) ctx->bank_k.push_back(k);
     ctx->nb = (int)ctx->bank_k.size();
     const int nb = ctx->nb;
@@ -738,81 +828,16 @@ extern "C" int avc_create(int device, const avc_se_cfg* cfgp, const float* w, si
     return 0;
 }
 
-static void free_plan(Plan& pl) {
-    for (Problem* p : pl.owned) hipFree(p);
-    pl.owned.clear();
-    pl.launches.clear();
-}
-
-static void free_plans(Workspace& ws) {
-    if (ws.graph) (void)hipGraphExecDestroy(ws.graph);
-    if (ws.graph_bf16) (void)hipGraphExecDestroy(ws.graph_bf16);
-    ws.graph = ws.graph_bf16 = nullptr;
-    for (int p = 0; p < 2; ++p) {
-        if (ws.hdr_graph[p]) (void)hipGraphExecDestroy(ws.hdr_graph[p]);
-        ws.hdr_graph[p] = nullptr;
-        free_plan(ws.hdr_it[p]);
-    }
-    free_plan(ws.fwd);
-    free_plan(ws.iter);
-    free_plan(ws.iter_bf16);
-}
-
-static void free_ws(Workspace& ws) {
-    free_plans(ws);
-    DevBuf* bufs[] = {&ws.xin, &ws.adv, &ws.vc, &ws.ptb, &ws.m, &ws.v, &ws.bank, &ws.h0, &ws.gbank, &ws.gxd,
-                      &ws.g1, &ws.ghx, &ws.ghy, &ws.gmx, &ws.gmy, &ws.emb_fwd, &ws.org, &ws.tgt, &ws.grad0, &ws.losses, &ws.table, &ws.scal, &ws.slab, &ws.pooled, &ws.gpooled, &ws.loss_cur,
-                      &ws.hdr, &ws.hdr_m, &ws.hdr_v, &ws.hdr_gx};
-    for (DevBuf* b : bufs) dfree(*b);
-    for (auto& b : ws.a1) dfree(b);
-    for (auto& b : ws.a2) dfree(b);
-    for (auto& b : ws.hb) dfree(b);
-    ws.a1.clear();
-    ws.a2.clear();
-    ws.hb.clear();
-    if (ws.step) hipFree(ws.step);
-    ws.step = nullptr;
-    if (ws.masks) hipFree(ws.masks);
-    ws.masks = nullptr;
-    if (ws.lza.img[0]) hipFree(ws.lza.img[0]);
-    if (ws.lza.fl[0]) hipFree(ws.lza.fl[0]);
-    if (ws.lza.masks) hipFree(ws.lza.masks);
-    ws.lza = LongArgs{};
-    if (ws.rag) hipFree(ws.rag);
-    ws.rag = nullptr;
-    ws.ragged = false;
-    ws.lens.clear();
-    ws.fused = false;
-    ws.lz = false;
-    ws.built = false;
-    ws.B = ws.T = 0;
-    ws.iters_cap = 0;
-}
-
 extern "C" void avc_destroy(avc_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     vc_free(ctx);
-    for (Workspace& w : ctx->wss) free_ws(w);
-    ctx->wss.clear();
-    ctx->cur = nullptr;
-    for (auto* v : {&ctx->AtF_bank, &ctx->AtF_c1, &ctx->AtF_c2, &ctx->AtB_c1, &ctx->AtB_c2, &ctx->bias_bank,
-                    &ctx->bias_c1, &ctx->bias_c2})
-        for (auto& b : *v) dfree(b);
-    for (DevBuf* b : {&ctx->AtF_in, &ctx->AtB_in, &ctx->AtB_bank, &ctx->bias_in, &ctx->head_Wp,
-                      &ctx->head_WpT, &ctx->head_bias, &ctx->head_Wr, &ctx->head_WrT, &ctx->head_Wr16,
-                      &ctx->head_WrT16})
-        dfree(*b);
-    for (auto& b : ctx->fz_bufs) dfree(b);
-    for (auto& kv : ctx->bf16_of) (void)hipFree(kv.second);
-    ctx->bf16_of.clear();
     if (ctx->ev_user) hipEventDestroy(ctx->ev_user);
     if (ctx->ev_done) hipEventDestroy(ctx->ev_done);
     if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    if (ctx->stage) (void)hipHostFree(ctx->stage);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // workspaces (graphs first), then the weights, free themselves
 }
 
 // ---------------------------------------------------------------------------------
@@ -865,7 +890,7 @@ static dim3 gemm_grid(const Launch& L, int variant) {
 // sum every output in the same order (bitwise shard invariance); the split
 // boundaries are multiples of KALIGN rows, so the tile variant cannot move them.
 static int choose_ksplit(const Problem& p, int nprob) {
-    if (const char* e = getenv("AVC_KSPLIT")) return std::max(1, std::min(KSPLIT_MAX, atoi(e)));
+    if (env_is("AVC_KSPLIT", 0)) return std::max(1, std::min(KSPLIT_MAX, env_int("AVC_KSPLIT", 1)));
     if (nprob > 1 || p.M > 128) return 1;
     const int kb = p.K / KALIGN;                 // K in KALIGN blocks
     int ks = 1;
@@ -923,7 +948,7 @@ static int add_gemm(avc_ctx* ctx, Plan& pl, std::vector<Problem> ps, double flop
     for (auto& p : ps) {
         auto it = ctx->bf16_of.find(p.At);
         if (it == ctx->bf16_of.end()) return fail("internal: no bf16 copy of an A matrix");
-        p.Ab = it->second;
+        p.Ab = it->second.get();
         for (int i = 0; i < p.nseg; ++i)
             if (p.seg[i].mode != ps[0].seg[0].mode || p.seg[i].stride != ps[0].seg[0].stride)
                 return fail("internal: mixed loader modes in one launch");
@@ -934,10 +959,10 @@ static int add_gemm(avc_ctx* ctx, Plan& pl, std::vector<Problem> ps, double flop
         gy = std::max(gy, p.M);
         minMpad = minMpad ? std::min(minMpad, p.Mpad) : p.Mpad;
     }
-    Problem* d = nullptr;
-    HIPCHK(hipMalloc(&d, ps.size() * sizeof(Problem)));
+    pl.owned.emplace_back();
+    if (dmalloc(pl.owned.back(), ps.size() * sizeof(Problem))) return 1;
+    Problem* d = pl.owned.back().get();
     HIPCHK(hipMemcpy(d, ps.data(), ps.size() * sizeof(Problem), hipMemcpyHostToDevice));
-    pl.owned.push_back(d);
     Launch L;
     L.kind = L_GEMM;
     L.prec = prec;
@@ -977,7 +1002,7 @@ static int plan_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float* x, b
             p.out0 = ws.bank.p;
             p.out0_C = nb * c.c_bank;
             p.out0_coff = i * c.c_bank;
-            if (attack && i == 0) p.tick = ws.step;
+            if (attack && i == 0) p.tick = ws.step.get();
             ps.push_back(p);
             flop += 2.0 * c.c_bank * c.c_in * k * N0;
         }
@@ -1035,7 +1060,7 @@ static int plan_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float* x, b
         A.tgt = ws.tgt.p;
         A.org = ws.org.p;
         A.losses = ws.losses.p;
-        A.step = ws.step;
+        A.step = ws.step.get();
         A.B = B;
         A.C = c.c_h;
         A.TN = ws.Tl[c.n_conv_blocks];
@@ -1131,7 +1156,7 @@ static int plan_backward(avc_ctx* ctx, Workspace& ws, Plan& pl, int prec) {
         if (nb > MAX_SEGS) return fail("bank_size/bank_scale > %d kernels not supported", MAX_SEGS);
         p.epi = EPI_ADAM;
         p.aux0 = ws.gxd.p;
-        p.step = ws.step;
+        p.step = ws.step.get();
         p.scal = ws.scal.p;
         p.table_len = ws.iters_cap;
         AdamArgs& A = p.adam;
@@ -1176,37 +1201,36 @@ static FusedArgs fused_args(avc_ctx* ctx, Workspace& ws, int prec) {
     for (int l = 0; l < c.n_conv_blocks; ++l) A.sub[l] = c.subsample[l];
     for (int l = 0; l <= c.n_conv_blocks; ++l) A.Tl[l] = ws.Tl[l];
     A.mask_words = ws.mask_words;
-    A.masks = ws.masks;
+    A.masks = ws.masks.get();
     A.pooled = ws.pooled.p;
     A.g_pooled = ws.gpooled.p;
-    A.step = ws.step;
+    A.step = ws.step.get();
     A.scal = ws.scal.p;
     A.table_len = ws.iters_cap;
     A.w = ctx->fzw[prec];
-    A.rag = ws.rag;
+    A.rag = ws.rag.get();
     return A;
 }
 
 // fused kernel shape: 0 = AdaIN-VC config.yaml defaults at T = 128 (every layer shape
 // compile-time), else the fragment bound 1|2|4|8 >= ceil(T/16)
-static int fused_shape(avc_ctx* ctx, int T) {
-    const avc_se_cfg& c = ctx->cfg;
-    bool std_cfg = T == 128 && ctx->nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
+static int enc_shape(const avc_se_cfg& c, int nb, int T) {
+    bool std_cfg = T == 128 && nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
     for (int l = 0; std_cfg && l < 6; ++l)
         if (c.subsample[l] != ((l & 1) ? 2 : 1)) std_cfg = false;
-    const char* e = getenv("AVC_FUSED_STD");
-    const char* rf = getenv("AVC_FUSED_RT_FORCE");   // A/B runs: the runtime-length kernels at T = 128 too
-    if (std_cfg && rf && rf[0] == '1') return 16;
-    if (std_cfg && !(e && e[0] == '0')) return 0;
+    const bool std_on = !env_is("AVC_FUSED_STD", '0');
+    if (std_cfg && env_is("AVC_FUSED_RT_FORCE", '1')) return 16;   // A/B runs: the runtime-length kernels at T = 128 too
+    if (std_cfg && std_on) return 0;
     // the standard config at 64 < T < 128: the standard kernels' fragment classes with runtime lengths
-    bool std_rt = T > 64 && T < 128 && ctx->nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
+    bool std_rt = T > 64 && T < 128 && nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
     for (int l = 0; std_rt && l < 6; ++l)
         if (c.subsample[l] != ((l & 1) ? 2 : 1)) std_rt = false;
-    const char* r = getenv("AVC_FUSED_RT");
-    if (std_rt && !(e && e[0] == '0') && !(r && r[0] == '0')) return 16;
+    if (std_rt && std_on && !env_is("AVC_FUSED_RT", '0')) return 16;
     const int nf = cdiv(T, 16);
     return nf <= 1 ? 1 : nf <= 2 ? 2 : nf <= 4 ? 4 : 8;
 }
+
+static int fused_shape(avc_ctx* ctx, int T) { return enc_shape(ctx->cfg, ctx->nb, T); }
 
 static int plan_fused_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float* x, bool attack, int prec) {
     const avc_se_cfg& c = ctx->cfg;
@@ -1218,10 +1242,10 @@ static int plan_fused_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float
     F.block = dim3(256);
     F.shmem = ws.lz ? LZ_SHMEM : fz_lds_fwd(prec, ws.T, c.kernel_size);
     F.fz = fused_args(ctx, ws, prec);
-    F.lz = ws.lza;
+    F.lz = ws.lzs.a;
     F.fz.x = x;
     F.fz.write_masks = attack ? 1 : 0;
-    F.fz.tick = attack ? ws.step : nullptr;
+    F.fz.tick = attack ? ws.step.get() : nullptr;
     F.fz_shape = ws.ragged ? 16 : fused_shape(ctx, ws.T);
     F.flop = ws.flop_fwd;
     F.name = prec == PREC_F32 ? "se_fwd_fused<f32>" : "se_fwd_fused<bf16>";
@@ -1249,7 +1273,7 @@ static int plan_fused_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float
     A.tgt = ws.tgt.p;
     A.org = ws.org.p;
     A.losses = ws.losses.p;
-    A.step = ws.step;
+    A.step = ws.step.get();
     A.B = B;
     A.C = c.c_h;
     A.TN = ws.Tl[c.n_conv_blocks];
@@ -1265,10 +1289,9 @@ static int plan_fused_forward(avc_ctx* ctx, Workspace& ws, Plan& pl, const float
 
     // emb attack in bf16: the head runs in the forward's tail (se_head_fused), one launch
     // fewer per iteration; AVC_FUSE_HEAD=0 keeps the separate se_head_v launch (A/B runs)
-    const char* fe = getenv("AVC_FUSE_HEAD");
     // (standard shape only: the in-kernel chain is unrolled for its n_dense = 6)
     if (attack && prec == PREC_BF16 && ctx->head_Wr16.p && c.c_h == FZ_C && c.c_out == FZ_C && !ws.lz && (F.fz_shape == 0 || F.fz_shape == 16) &&
-        c.n_dense_blocks == 6 && !(fe && fe[0] == '0')) {
+        c.n_dense_blocks == 6 && !env_is("AVC_FUSE_HEAD", '0')) {
         const size_t head_lds = (size_t)(4 * c.n_dense_blocks + 8) * FZ_C * sizeof(float);
         F.shmem = std::max(F.shmem, head_lds);
         F.fz.fuse_head = 1;
@@ -1291,7 +1314,7 @@ static int plan_fused_backward(avc_ctx* ctx, Workspace& ws, Plan& pl, int prec) 
     L.grid = dim3(ws.B);
     L.block = dim3(256);
     L.fz = fused_args(ctx, ws, prec);
-    L.lz = ws.lza;
+    L.lz = ws.lzs.a;
     L.fz_shape = ws.ragged ? 16 : fused_shape(ctx, ws.T);
     // (SH = 16: the LDS images are laid out for the 128-frame bound)
     L.shmem = ws.lz ? LZ_SHMEM : fz_lds_bwd_launch(prec, L.fz_shape == 16 ? 128 : ws.T, L.fz_shape, L.fz.mask_words);
@@ -1339,16 +1362,13 @@ static int autotune(avc_ctx* ctx, Plan& pl);
 // configs neither is built for.  AVC_FUSED=0 (AUTO only) forces layered, AVC_LONG=1 long.
 static int engine_for(avc_ctx* ctx, int T) {
     if (ctx->engine == AVC_ENGINE_LAYERED || !ctx->fused_ok) return AVC_ENGINE_LAYERED;
-    const char* fe = getenv("AVC_FUSED");
-    if (ctx->engine == AVC_ENGINE_AUTO && fe && fe[0] == '0') return AVC_ENGINE_LAYERED;
-    const char* le = getenv("AVC_LONG");
-    if (ctx->engine == AVC_ENGINE_LONG || (le && le[0] == '1')) return AVC_ENGINE_LONG;
+    if (ctx->engine == AVC_ENGINE_AUTO && env_is("AVC_FUSED", '0')) return AVC_ENGINE_LAYERED;
+    if (ctx->engine == AVC_ENGINE_LONG || env_is("AVC_LONG", '1')) return AVC_ENGINE_LONG;
     return T <= 128 ? AVC_ENGINE_FUSED : AVC_ENGINE_LONG;
 }
-static bool want_fused(avc_ctx* ctx, int T) { return engine_for(ctx, T) != AVC_ENGINE_LAYERED; }
-
 // long-engine scratch for B utterances of up to T frames and `nlayers` masked layers
-static int alloc_long(LongArgs& L, int B, int T, int nlayers) {
+static int alloc_long(LongScratch& S, int B, int T, int nlayers) {
+    LongArgs& L = S.a;
     // pad rows around the frames, + LZ_ZR for the decoder's out_conv^T dY image (zeroed over
     // Tn + 3 LZ_ZR rows).  Every stage of a chunk window is clipped to these rows in the kernels
     // (avc_long.hip LzPipe::rows / lz_stage_cap): a stride-2 window spans 2 * 127 + k + 2 rows whatever
@@ -1358,49 +1378,20 @@ static int alloc_long(LongArgs& L, int B, int T, int nlayers) {
     L.fl_stride = (int64_t)((T + 32 + 15) / 16 + LZ_FL_EXTRA) * 4 * 2 * 64 * 4;
     L.nFmax = (T + 15) / 16;
     L.mask_stride = (int64_t)nlayers * L.nFmax * 32;
-    // each allocation is recorded in L at once, so free_ws releases a partial set on failure
-    char* img = nullptr;
-    float* fl = nullptr;
-    unsigned long long* mk = nullptr;
-    HIPCHK(hipMalloc(&img, 3 * (size_t)B * L.img_stride));
-    L.img[0] = img;
-    HIPCHK(hipMalloc(&fl, 3 * (size_t)B * L.fl_stride * sizeof(float)));
-    L.fl[0] = fl;
-    HIPCHK(hipMalloc(&mk, (size_t)B * L.mask_stride * sizeof(unsigned long long)));
-    L.masks = mk;
+    const size_t n_img = 3 * (size_t)B * L.img_stride, n_fl = 3 * (size_t)B * L.fl_stride * sizeof(float),
+                 n_mk = (size_t)B * L.mask_stride * sizeof(unsigned long long);
+    if (dmalloc(S.img, n_img) || dmalloc(S.fl, n_fl) || dmalloc(S.masks, n_mk)) return 1;
     // every byte a kernel may stage is finite from the start (weights past K are zero, and
     // 0 * NaN would not be)
-    HIPCHK(hipMemset(img, 0, 3 * (size_t)B * L.img_stride));
-    HIPCHK(hipMemset(fl, 0, 3 * (size_t)B * L.fl_stride * sizeof(float)));
-    HIPCHK(hipMemset(mk, 0, (size_t)B * L.mask_stride * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(S.img.get(), 0, n_img));
+    HIPCHK(hipMemset(S.fl.get(), 0, n_fl));
+    HIPCHK(hipMemset(S.masks.get(), 0, n_mk));
+    L.masks = S.masks.get();
     for (int i = 0; i < 3; ++i) {
-        L.img[i] = img + (size_t)i * B * L.img_stride;
-        L.fl[i] = fl + (size_t)i * B * L.fl_stride;
+        L.img[i] = S.img.get() + (size_t)i * B * L.img_stride;
+        L.fl[i] = S.fl.get() + (size_t)i * B * L.fl_stride;
     }
     return 0;
-}
-
-// a workspace whose build failed part-way: release what it holds and forget it (returns 1)
-static int drop_ws(avc_ctx* ctx);
-// HIPCHK for a workspace under construction: on failure the half-built entry is dropped (drop_ws)
-#define WSCHK(expr)                                                                                   \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);      \
-            return drop_ws(ctx);                                                                  \
-        }                                                                                         \
-    } while (0)
-static int drop_ws(avc_ctx* ctx) {
-    for (auto it = ctx->wss.begin(); it != ctx->wss.end(); ++it)
-        if (&*it == ctx->cur) {
-            (void)hipStreamSynchronize(ctx->stream);
-            free_ws(*it);
-            ctx->wss.erase(it);
-            break;
-        }
-    ctx->cur = nullptr;
-    return 1;
 }
 
 // lengths through the conv blocks for T input frames + reflect-pad validity (torch: pad < input length)
@@ -1429,155 +1420,149 @@ static int enc_block_lengths(avc_ctx* ctx, int T, std::vector<int>& Tl) {
     return 0;
 }
 
-// The workspace of a call: B utterances of T frames, or (lens non-null) a ragged batch of B utterances
-// of lens[b] frames (long engine; T is ignored).  Cached by shape, most recently used first.
-static int ensure_ws(avc_ctx* ctx, int B, int T, int n_iters, const std::vector<int>* lens = nullptr) {
-    const avc_se_cfg& c = ctx->cfg;
+// The cache key of a call: B utterances of T frames, or (lens non-null) a ragged batch of B utterances of
+// lens[b] frames.  A ragged batch runs the fused runtime-length kernels with a per-workgroup length when
+// every length is in (64, 128] of the standard config (T = 128 is then the workspace's bound: LDS layout,
+// mask words), otherwise the long engine at T = the longest; never the layered engine.
+static int resolve_key(avc_ctx* ctx, int B, int T, const std::vector<int>* lens, SeKey& k) {
     if (B <= 0) return fail("batch size must be positive (got %d)", B);
-    std::vector<int> Tl;
-    std::vector<std::vector<int>> Tls;
-    double flop = 0;
-    size_t X = 0;
-    bool rag_fused = false;
-    if (lens) {
-        if ((int)lens->size() != B) return fail("ragged batch: %zu lengths for B=%d", lens->size(), B);
-        if (!ctx->fused_ok || ctx->engine == AVC_ENGINE_LAYERED)
-            return fail("ragged batches run on the long engine (fused-capable config, engine not layered)");
-        T = *std::max_element(lens->begin(), lens->end());
-        // every length in (64, 128] of the standard config: the fused runtime-length kernels with a
-        // per-workgroup length (LDS images laid out for 128 frames); otherwise the long engine
-        const int Tmin = *std::min_element(lens->begin(), lens->end());
-        const char* rf = getenv("AVC_RAGGED_FUSED");
-        rag_fused = Tmin > 64 && T <= 128 && ctx->engine != AVC_ENGINE_LONG && !(rf && rf[0] == '0') &&
-                    fused_shape(ctx, 100) == 16 && !(getenv("AVC_LONG") && getenv("AVC_LONG")[0] == '1');
-        for (int b = 0; b < B; ++b) {
-            std::vector<int> t;
-            if (enc_block_lengths(ctx, (*lens)[b], t)) return 1;
-            flop += fz_fwd_flop(c, t, ctx->bank_k);
-            X += (size_t)c.c_in * (*lens)[b];
-            Tls.push_back(t);
-        }
-    }
-    if (rag_fused) T = 128;   // the workspace's bound (LDS layout, mask words); lengths come from ws.rag
-    if (enc_block_lengths(ctx, T, Tl)) return 1;
+    k.B = B;
     if (!lens) {
-        flop = fz_fwd_flop(c, Tl, ctx->bank_k) * B;
-        X = (size_t)B * c.c_in * T;
+        k.T = T;
+        k.engine = engine_for(ctx, T);
+        return 0;
     }
-    const int eng = lens ? (rag_fused ? AVC_ENGINE_FUSED : AVC_ENGINE_LONG) : engine_for(ctx, T);
-    const bool fused = eng != AVC_ENGINE_LAYERED, lz = eng == AVC_ENGINE_LONG;
-    // a cached workspace of this shape (most recently used first)
-    auto it = ctx->wss.begin();
-    for (; it != ctx->wss.end(); ++it)
-        if (it->built && it->ragged == (lens != nullptr) &&
-            (lens ? it->lens == *lens : (it->B == B && it->T == T && it->fused == fused && it->lz == lz)))
-            break;
-    static const bool dbg_ws = getenv("AVC_DEBUG_WS") && getenv("AVC_DEBUG_WS")[0] == '1';
-    if (dbg_ws)
-        fprintf(stderr, "AVC_DEBUG_WS ensure_ws B=%d T=%d fused=%d lz=%d ragged=%d n=%d: %s (%zu cached)\n", B, T,
-                (int)fused, (int)lz, (int)(lens != nullptr), n_iters, it != ctx->wss.end() ? "hit" : "new", ctx->wss.size());
-    if (it != ctx->wss.end()) {
-        ctx->wss.splice(ctx->wss.begin(), ctx->wss, it);
-        ctx->cur = &ctx->wss.front();
-        if (n_iters <= ctx->cur->iters_cap) {
-            ++ctx->n_ws_hits;
-            return 0;
+    if ((int)lens->size() != B) return fail("ragged batch: %zu lengths for B=%d", lens->size(), B);
+    if (!ctx->fused_ok || ctx->engine == AVC_ENGINE_LAYERED)
+        return fail("ragged batches run on the long engine (fused-capable config, engine not layered)");
+    const int Tmin = *std::min_element(lens->begin(), lens->end());
+    const int Tmax = *std::max_element(lens->begin(), lens->end());
+    const bool rag_fused = Tmin > 64 && Tmax <= 128 && ctx->engine != AVC_ENGINE_LONG && !env_is("AVC_RAGGED_FUSED", '0') &&
+                           fused_shape(ctx, 100) == 16 && !env_is("AVC_LONG", '1');
+    k.T = rag_fused ? 128 : Tmax;
+    k.engine = rag_fused ? AVC_ENGINE_FUSED : AVC_ENGINE_LONG;
+    k.lens = *lens;
+    return 0;
+}
+
+// a workspace whose build or plan failed part-way: forget it (its owners free what it holds); returns 1
+static int drop_cur(avc_ctx* ctx) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->wss.erase(ctx->cur);
+    ctx->cur = nullptr;
+    return 1;
+}
+
+// the buffers of a new workspace for key `k`
+static int build_ws(avc_ctx* ctx, Workspace& ws, const SeKey& k) {
+    const avc_se_cfg& c = ctx->cfg;
+    const int B = k.B, T = k.T, nb = ctx->nb;
+    ws.B = B;
+    ws.T = T;
+    ws.fused = k.engine != AVC_ENGINE_LAYERED;
+    ws.lz = k.engine == AVC_ENGINE_LONG;
+    ws.ragged = !k.lens.empty();
+    if (enc_block_lengths(ctx, T, ws.Tl)) return 1;
+    if (ws.ragged) {
+        std::vector<RagUtt> ru(B);
+        std::vector<int> t;
+        for (int b = 0; b < B; ++b) {
+            if (enc_block_lengths(ctx, k.lens[b], t)) return 1;
+            ws.flop_fwd += fz_fwd_flop(c, t, ctx->bank_k);
+            ru[b] = RagUtt{};
+            ru[b].T = k.lens[b];
+            ru[b].xoff = (int64_t)ws.X;
+            ws.X += (size_t)c.c_in * k.lens[b];
         }
+        if (dmalloc(ws.rag, B * sizeof(RagUtt))) return 1;
+        HIPCHK(hipMemcpy(ws.rag.get(), ru.data(), B * sizeof(RagUtt), hipMemcpyHostToDevice));
     } else {
-        // a new shape: make room (the stream may still use an evicted workspace's buffers)
-        const char* ce = getenv("AVC_WS_CACHE");
-        const int cap = std::max(1, ce ? atoi(ce) : ctx->ws_cap);
-        while ((int)ctx->wss.size() >= cap) {
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (dbg_ws)
-                fprintf(stderr, "AVC_DEBUG_WS evict ws B=%d T=%d lz=%d gen=%d\n", ctx->wss.back().B, ctx->wss.back().T,
-                        (int)ctx->wss.back().lz, ctx->wss.back().gen);
-            free_ws(ctx->wss.back());
-            ctx->wss.pop_back();
-            ++ctx->n_ws_evictions;
+        ws.flop_fwd = fz_fwd_flop(c, ws.Tl, ctx->bank_k) * B;
+        ws.X = (size_t)B * c.c_in * T;
+    }
+    const size_t X = ws.X;
+    int rc = 0;
+    for (DevBuf* b : {&ws.xin, &ws.adv, &ws.vc, &ws.ptb, &ws.m, &ws.v, &ws.grad0}) rc |= dalloc(*b, X);
+    for (DevBuf* b : {&ws.emb_fwd, &ws.org, &ws.tgt}) rc |= dalloc(*b, (size_t)B * c.c_out);
+    if (ws.fused) {
+        ws.mask_words = (nb + 1 + 2 * c.n_conv_blocks) * FZ_MASK_WORDS_PER_LAYER;
+        rc |= dalloc(ws.pooled, (size_t)B * FZ_C);
+        rc |= dalloc(ws.gpooled, (size_t)B * FZ_C);
+        rc |= dalloc(ws.loss_cur, (size_t)B);
+        if (rc || dmalloc(ws.masks, (size_t)B * ws.mask_words * sizeof(unsigned long long))) return 1;
+        if (ws.lz && alloc_long(ws.lzs, B, T, nb + 1 + 2 * c.n_conv_blocks)) return 1;
+    } else {
+        rc |= dalloc(ws.gxd, X);
+        rc |= dalloc(ws.bank, (size_t)B * nb * c.c_bank * T);
+        rc |= dalloc(ws.gbank, (size_t)B * nb * c.c_bank * T);
+        const size_t H = (size_t)B * c.c_h * T;
+        for (DevBuf* b : {&ws.h0, &ws.g1, &ws.ghx, &ws.ghy, &ws.gmx, &ws.gmy}) rc |= dalloc(*b, H);
+        ws.a1.resize(c.n_conv_blocks);
+        ws.a2.resize(c.n_conv_blocks);
+        ws.hb.resize(c.n_conv_blocks);
+        for (int l = 0; l < c.n_conv_blocks; ++l) {
+            rc |= dalloc(ws.a1[l], (size_t)B * c.c_h * ws.Tl[l]);
+            rc |= dalloc(ws.a2[l], (size_t)B * c.c_h * ws.Tl[l + 1]);
+            rc |= dalloc(ws.hb[l], (size_t)B * c.c_h * ws.Tl[l + 1]);
         }
-        ctx->wss.emplace_front();
-        ctx->cur = &ctx->wss.front();
+        rc |= dalloc(ws.slab, (size_t)KSPLIT_MAX * std::max(c.c_h, c.c_in) * B * T);
+    }
+    return rc || dmalloc(ws.step, sizeof(int)) || dalloc(ws.scal, 8);
+}
+
+// one iteration plan of `ws` at `prec`, its GEMM tiles autotuned with valid scalars: Adam step 1
+// and eps / gscale 0.1 (the kernels clamp anyway).  Blocking copies: the stream must be idle.
+static int plan_tuned_iteration(avc_ctx* ctx, Workspace& ws, Plan& pl, int prec, Plan* tune_first = nullptr) {
+    if (plan_iteration(ctx, ws, pl, prec)) return 1;
+    const float scal0[8] = {0.1f, 0.f, 0.f, 0.f, 0.1f, 0.f, 0.f, 0.f};
+    HIPCHK(hipMemcpy(ws.scal.p, scal0, sizeof(scal0), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(ws.step.get(), 0, sizeof(int)));
+    if (tune_first && autotune(ctx, *tune_first)) return 1;
+    return autotune(ctx, pl);
+}
+
+// tables for `cap` iterations and the fp32 plans of `ws` (the bf16 plan is built on demand);
+// the buffers may have moved, so every plan and graph starts over
+static int plan_ws(avc_ctx* ctx, Workspace& ws, int cap) {
+    if (dalloc(ws.losses, (size_t)cap * ws.B) || dalloc(ws.table, (size_t)cap * 2)) return 1;
+    ws.iters_cap = cap;
+    renew(ws.pl);
+    ws.gen = ++ctx->gen_next;
+    if (ws.fused ? plan_fused_forward(ctx, ws, ws.pl.fwd, ws.xin.p, false, PREC_F32)
+                 : plan_forward(ctx, ws, ws.pl.fwd, ws.xin.p, false, PREC_F32))
+        return 1;
+    return plan_tuned_iteration(ctx, ws, ws.pl.iter, PREC_F32, &ws.pl.fwd);
+}
+
+// The workspace of a call (ctx->cur) with tables for n_iters iterations: resolve the key, look it
+// up, build a new entry or re-plan one whose tables are too short, plan.
+static int ensure_ws(avc_ctx* ctx, int B, int T, int n_iters, const std::vector<int>* lens = nullptr) {
+    SeKey k;
+    if (resolve_key(ctx, B, T, lens, k)) return 1;
+    ctx->cur = ctx->wss.find(k);
+    if (ctx->cur && n_iters <= ctx->cur->iters_cap) {
+        ++ctx->n_ws_hits;
+        return 0;
+    }
+    const bool fresh = !ctx->cur;
+    // making room, and re-planning, wait for the stream: it may still use the buffers
+    auto quiesce = [&] { return hipStreamSynchronize(ctx->stream) != hipSuccess; };
+    if (fresh) {
+        std::vector<int> t;   // the key's lengths are valid before anything is evicted for it
+        for (int len : k.lens)
+            if (enc_block_lengths(ctx, len, t)) return 1;
+        if (enc_block_lengths(ctx, k.T, t)) return 1;
+        ctx->cur = ctx->wss.insert(k, env_int("AVC_WS_CACHE", ctx->wss.cap), quiesce);
+        if (!ctx->cur) return fail("hipStreamSynchronize failed before a workspace eviction");
+    }
+    if (quiesce()) {
+        fail("hipStreamSynchronize failed");
+        return drop_cur(ctx);
     }
     Workspace& ws = *ctx->cur;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (!ws.built) {
-        ++ctx->n_ws_builds;
-        ws.B = B;
-        ws.T = T;
-        ws.Tl = Tl;
-        ws.X = X;
-        ws.flop_fwd = flop;
-        const int nb = ctx->nb;
-        ws.fused = fused;
-        ws.lz = lz;
-        if (lens) {
-            ws.ragged = true;
-            ws.lens = *lens;
-            std::vector<RagUtt> ru(B);
-            int64_t off = 0;
-            for (int b = 0; b < B; ++b) {
-                ru[b] = RagUtt{};
-                ru[b].T = (*lens)[b];
-                ru[b].xoff = off;
-                off += (int64_t)c.c_in * (*lens)[b];
-            }
-            WSCHK(hipMalloc(&ws.rag, B * sizeof(RagUtt)));
-            WSCHK(hipMemcpy(ws.rag, ru.data(), B * sizeof(RagUtt), hipMemcpyHostToDevice));
-        }
-        int rc = 0;
-        for (DevBuf* b : {&ws.xin, &ws.adv, &ws.vc, &ws.ptb, &ws.m, &ws.v, &ws.grad0}) rc |= dalloc(*b, X);
-        for (DevBuf* b : {&ws.emb_fwd, &ws.org, &ws.tgt}) rc |= dalloc(*b, (size_t)B * c.c_out);
-        if (ws.fused) {
-            ws.mask_words = (nb + 1 + 2 * c.n_conv_blocks) * FZ_MASK_WORDS_PER_LAYER;
-            rc |= dalloc(ws.pooled, (size_t)B * FZ_C);
-            rc |= dalloc(ws.gpooled, (size_t)B * FZ_C);
-            rc |= dalloc(ws.loss_cur, (size_t)B);
-            if (rc) return drop_ws(ctx);
-            WSCHK(hipMalloc(&ws.masks, (size_t)B * ws.mask_words * sizeof(unsigned long long)));
-            if (ws.lz && alloc_long(ws.lza, B, T, nb + 1 + 2 * c.n_conv_blocks)) return drop_ws(ctx);
-        } else {
-            rc |= dalloc(ws.gxd, X);
-            rc |= dalloc(ws.bank, (size_t)B * nb * c.c_bank * T);
-            rc |= dalloc(ws.gbank, (size_t)B * nb * c.c_bank * T);
-            const size_t H = (size_t)B * c.c_h * T;
-            for (DevBuf* b : {&ws.h0, &ws.g1, &ws.ghx, &ws.ghy, &ws.gmx, &ws.gmy}) rc |= dalloc(*b, H);
-            ws.a1.resize(c.n_conv_blocks);
-            ws.a2.resize(c.n_conv_blocks);
-            ws.hb.resize(c.n_conv_blocks);
-            for (int l = 0; l < c.n_conv_blocks; ++l) {
-                rc |= dalloc(ws.a1[l], (size_t)B * c.c_h * Tl[l]);
-                rc |= dalloc(ws.a2[l], (size_t)B * c.c_h * Tl[l + 1]);
-                rc |= dalloc(ws.hb[l], (size_t)B * c.c_h * Tl[l + 1]);
-            }
-            rc |= dalloc(ws.slab, (size_t)KSPLIT_MAX * std::max(c.c_h, c.c_in) * B * T);
-        }
-        if (rc) return drop_ws(ctx);
-        WSCHK(hipMalloc(&ws.step, sizeof(int)));
-        if (dalloc(ws.scal, 8)) return drop_ws(ctx);
-    } else {
-        ++ctx->n_ws_replans;   // more iterations than this workspace's tables hold
-    }
-    const int cap = std::max(n_iters, std::max(ws.iters_cap, 1));
-    if (dalloc(ws.losses, (size_t)cap * B)) return drop_ws(ctx);
-    if (dalloc(ws.table, (size_t)cap * 2)) return drop_ws(ctx);
-    ws.iters_cap = cap;
-    // (re)build plans: pointers may have moved (the bf16 plan is rebuilt on demand)
-    free_plans(ws);
-    ws.built = false;
-    ws.gen = ++ctx->gen_next;
-    if (ws.fused) {
-        if (plan_fused_forward(ctx, ws, ws.fwd, ws.xin.p, false, PREC_F32)) return drop_ws(ctx);
-    } else {
-        if (plan_forward(ctx, ws, ws.fwd, ws.xin.p, false, PREC_F32)) return drop_ws(ctx);
-    }
-    if (plan_iteration(ctx, ws, ws.iter, PREC_F32)) return drop_ws(ctx);
-    // autotune with a valid Adam step (1) and eps/gscale (the kernels clamp anyway)
-    const float scal0[8] = {0.1f, 0.f, 0.f, 0.f, 0.1f, 0.f, 0.f, 0.f};
-    WSCHK(hipMemcpy(ws.scal.p, scal0, sizeof(scal0), hipMemcpyHostToDevice));
-    WSCHK(hipMemset(ws.step, 0, sizeof(int)));
-    if (autotune(ctx, ws.fwd) || autotune(ctx, ws.iter)) return drop_ws(ctx);
-    ws.built = true;
+    ++(fresh ? ctx->n_ws_builds : ctx->n_ws_replans);
+    if (fresh && build_ws(ctx, ws, k)) return drop_cur(ctx);
+    if (plan_ws(ctx, ws, std::max(n_iters, std::max(ws.iters_cap, 1)))) return drop_cur(ctx);
     return 0;
 }
 
@@ -1731,13 +1716,13 @@ static std::string tune_key(avc_ctx* ctx, const Plan& pl, size_t li) {
     char buf[256];
     const avc_se_cfg& c = ctx->cfg;
     snprintf(buf, sizeof(buf), "B%d_T%d_ch%d_%d_%d_nb%d_%s_l%zu", ctx->cur->B, ctx->cur->T, c.c_in, c.c_h, c.c_bank,
-             c.n_conv_blocks, &pl == &ctx->cur->fwd ? "fwd" : (&pl == &ctx->cur->iter ? "iter" : "iterbf16"), li);
+             c.n_conv_blocks, &pl == &ctx->cur->pl.fwd ? "fwd" : (&pl == &ctx->cur->pl.iter ? "iter" : "iterbf16"), li);
     return buf;
 }
 
 static std::map<std::string, int> read_tune_file() {
     std::map<std::string, int> m;
-    const char* path = getenv("AVC_TUNE_FILE");
+    const char* path = getenv("AVC_TUNE_FILE");   // (a path: not a switch for env_is / env_int)
     if (!path) return m;
     FILE* f = fopen(path, "r");
     if (!f) return m;
@@ -1751,8 +1736,8 @@ static std::map<std::string, int> read_tune_file() {
 // AVC_PRINT_PLAN=1: one stderr line per launch of a tuned plan (position, layer,
 // kernel, grid, split-K) -- lets a rocprofv3 trace be read layer by layer.
 static void print_plan(avc_ctx* ctx, const Plan& pl) {
-    if (!getenv("AVC_PRINT_PLAN")) return;
-    const char* tag = &pl == &ctx->cur->fwd ? "fwd" : (&pl == &ctx->cur->iter ? "iter" : "iterbf16");
+    if (!env_is("AVC_PRINT_PLAN", 0)) return;
+    const char* tag = &pl == &ctx->cur->pl.fwd ? "fwd" : (&pl == &ctx->cur->pl.iter ? "iter" : "iterbf16");
     for (size_t i = 0; i < pl.launches.size(); ++i) {
         const Launch& L = pl.launches[i];
         const dim3 g = L.kind == L_GEMM ? gemm_grid(L, L.variant) : L.grid;
@@ -1770,8 +1755,7 @@ static int autotune(avc_ctx* ctx, Plan& pl) {
 }
 
 static int autotune_(avc_ctx* ctx, Plan& pl) {
-    const char* env = getenv("AVC_AUTOTUNE");
-    if (env && env[0] == '0') return 0;
+    if (env_is("AVC_AUTOTUNE", '0')) return 0;
     std::map<std::string, int> cache = read_tune_file();
     bool all_cached = true;
     for (size_t li = 0; li < pl.launches.size(); ++li) {
@@ -1836,7 +1820,7 @@ static int run_plan(avc_ctx* ctx, const Plan& pl, bool prof) {
     KEv ev;
     if (prof)
         for (hipEvent_t* e : {&ev.gemm0, &ev.gemm1, &ev.red0, &ev.red1}) HIPCHK(hipEventCreate(e));
-    static const bool dbg_sync = getenv("AVC_DEBUG_SYNC") && getenv("AVC_DEBUG_SYNC")[0] == '1';
+    static const bool dbg_sync = env_is("AVC_DEBUG_SYNC", '1');
     for (const Launch& L : pl.launches) {
         hipError_t e = launch_one(L, ctx->stream, prof ? &ev : nullptr);
         if (e != hipSuccess) return fail("launch %s: %s", kernel_name(L).c_str(), hipGetErrorString(e));
@@ -1858,7 +1842,7 @@ static int run_plan(avc_ctx* ctx, const Plan& pl, bool prof) {
         const std::string nm = kernel_name(L);
         prof_add(ctx, nm, ms, L.flop);
         if (red) prof_add(ctx, "splitk_reduce", ms_red, 0.0);
-        if (getenv("AVC_PROFILE_ROLES"))   // per-layer breakdown (diagnostics), reduce included
+        if (env_is("AVC_PROFILE_ROLES", 0))   // per-layer breakdown (diagnostics), reduce included
             prof_add(ctx, "role:" + L.name + "|" + nm, ms + ms_red, L.flop);
     }
     if (prof)
@@ -1879,18 +1863,23 @@ static int end_call(avc_ctx* ctx, hipStream_t user) {
     return 0;
 }
 
+static int d2d(avc_ctx* ctx, void* dst, const void* src, size_t nfloat) {
+    HIPCHK(hipMemcpyAsync(dst, src, nfloat * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+// emb of x (one input array of the workspace's shape) into ws.emb_fwd (fp32 forward plan)
+static int se_embed(avc_ctx* ctx, const float* x) {
+    Workspace& ws = *ctx->cur;
+    return d2d(ctx, ws.xin.p, x, ws.X) || run_plan(ctx, ws.pl.fwd, false);
+}
+
 extern "C" int avc_se_forward(avc_ctx* ctx, const float* x, int B, int T, float* emb, void* stream) {
     if (!ctx || !x || !emb) return fail("avc_se_forward: null argument");
     hipStream_t us = (hipStream_t)stream;
     if (ensure_ws(ctx, B, T, 1)) return 1;
     if (begin_call(ctx, us)) return 1;
-    Workspace& ws = *ctx->cur;
-    const avc_se_cfg& c = ctx->cfg;
-    HIPCHK(hipMemcpyAsync(ws.xin.p, x, (size_t)B * c.c_in * T * sizeof(float), hipMemcpyDeviceToDevice,
-                          ctx->stream));
-    if (run_plan(ctx, ws.fwd, false)) return 1;
-    HIPCHK(hipMemcpyAsync(emb, ws.emb_fwd.p, (size_t)B * c.c_out * sizeof(float), hipMemcpyDeviceToDevice,
-                          ctx->stream));
+    if (se_embed(ctx, x) || d2d(ctx, emb, ctx->cur->emb_fwd.p, (size_t)B * ctx->cfg.c_out)) return 1;
     return end_call(ctx, us);
 }
 
@@ -1968,13 +1957,14 @@ static int stage_call_consts(avc_ctx* ctx, int n_iters, const float scal[4], dou
     const size_t nt = 2 * (size_t)std::max(n_iters, 1);
     HIPCHK(hipEventSynchronize(ctx->ev_stage));   // the previous call's staging copies are done
     if (ctx->stage_n < nt + 8) {
-        if (ctx->stage) (void)hipHostFree(ctx->stage);
-        ctx->stage = nullptr;
+        ctx->stage.reset();
         ctx->stage_n = 0;
-        HIPCHK(hipHostMalloc((void**)&ctx->stage, (nt + 8) * sizeof(float), hipHostMallocDefault));
+        void* h = nullptr;
+        HIPCHK(hipHostMalloc(&h, (nt + 8) * sizeof(float), hipHostMallocDefault));
+        ctx->stage.reset(static_cast<float*>(h));
         ctx->stage_n = nt + 8;
     }
-    float* table = ctx->stage;
+    float* table = ctx->stage.get();
     for (size_t i = 0; i < nt; ++i) table[i] = 0.f;
     for (int t = 1; t <= n_iters; ++t) {   // step t0 + t of the optimiser (t0 steps taken before this call)
         const double bc1 = 1.0 - std::pow(beta1, t0 + t);
@@ -2000,11 +1990,9 @@ static int stage_call_consts(avc_ctx* ctx, int n_iters, const float scal[4], dou
 // in its tail and the fused backward + Adam, at the standard shape (T = 128), runs all its iterations in ONE launch
 // (then fz_step_add advances the step counter by as many).  AVC_PERSIST=0 keeps the per-pass launches.
 static bool persist_ok(const Plan& iter) {
-    const char* e = getenv("AVC_PERSIST");   // (read per call: tests compare both paths in one process)
-    const bool off = e && e[0] == '0';
-    const char* e16 = getenv("AVC_PERSIST16");   // A/B: the runtime-length shape on per-pass launches
-    const bool persist16_off = e16 && e16[0] == '0';
-    if (off || iter.launches.size() != 2) return false;
+    // (read per call: tests compare both paths in one process)
+    const bool persist16_off = env_is("AVC_PERSIST16", '0');   // A/B: the runtime-length shape on per-pass launches
+    if (env_is("AVC_PERSIST", '0') || iter.launches.size() != 2) return false;
     const Launch& F = iter.launches[0];
     const Launch& Bk = iter.launches[1];
     return F.kind == L_FZ_FWD && Bk.kind == L_FZ_BWD && F.prec == PREC_BF16 && Bk.prec == PREC_BF16 &&
@@ -2030,7 +2018,7 @@ static int run_persist(avc_ctx* ctx, const Plan& iter, int n_iters) {
 }
 
 constexpr int GRAPH_ITERS = 50;
-static int graph_replay(avc_ctx* ctx, Plan& iter, hipGraphExec_t& graph, int n_iters) {
+static int graph_replay(avc_ctx* ctx, Plan& iter, GraphExec& graph, int n_iters) {
     const int nfull = n_iters / GRAPH_ITERS;
     if (nfull > 0 && !graph) {
         hipGraph_t g;
@@ -2042,17 +2030,88 @@ static int graph_replay(avc_ctx* ctx, Plan& iter, hipGraphExec_t& graph, int n_i
         if (rc) return 1;
         if (e != hipSuccess) return fail("graph capture: %s", hipGetErrorString(e));
         ++ctx->n_graph_captures;
-        e = hipGraphInstantiate(&graph, g, nullptr, nullptr, 0);
+        hipGraphExec_t ge = nullptr;
+        e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
-        if (e != hipSuccess) {
-            graph = nullptr;
-            return fail("graph instantiate: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail("graph instantiate: %s", hipGetErrorString(e));
+        graph.reset(ge);
     }
-    for (int it = 0; it < nfull; ++it) HIPCHK(hipGraphLaunch(graph, ctx->stream));
+    for (int it = 0; it < nfull; ++it) HIPCHK(hipGraphLaunch(graph.get(), ctx->stream));
     for (int it = nfull * GRAPH_ITERS; it < n_iters; ++it)
         if (run_plan(ctx, iter, false)) return 1;
     return 0;
+}
+
+// n_iters profiled iterations between two events (avc_get_profile's ms per iteration)
+static int run_profiled(avc_ctx* ctx, const Plan& iter, int n_iters, hipEvent_t a, hipEvent_t b) {
+    HIPCHK(hipEventRecord(a, ctx->stream));
+    for (int it = 0; it < n_iters; ++it)
+        if (run_plan(ctx, iter, true)) return 1;
+    HIPCHK(hipEventRecord(b, ctx->stream));
+    HIPCHK(hipEventSynchronize(b));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, a, b));
+    ctx->prof_iter_ms += ms;
+    ctx->prof_iters += n_iters;
+    return 0;
+}
+
+// n_iters iterations of `iter` on the ctx stream, for every attack and the header optimiser: per-kernel
+// profiling, else the persistent kernel where the plan allows it, else graph replay (captured once
+// per plan), else plain launches
+static int run_iterations(avc_ctx* ctx, Plan& iter, GraphExec& graph, int n_iters, bool use_graph) {
+    if (ctx->profiling) {
+        hipEvent_t a = nullptr, b = nullptr;
+        int rc = 1;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) fail("hipEventCreate failed");
+        else rc = run_profiled(ctx, iter, n_iters, a, b);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        return rc;
+    }
+    if (persist_ok(iter)) return run_persist(ctx, iter, n_iters);
+    if (use_graph && n_iters > 0 && !env_is("AVC_NO_GRAPH", '1')) return graph_replay(ctx, iter, graph, n_iters);
+    for (int it = 0; it < n_iters; ++it)
+        if (run_plan(ctx, iter, false)) return 1;
+    return 0;
+}
+
+// avc_attack_opts with its defaults filled in (opts null: fp32, independent, Adam, graph replay)
+static int attack_opts(const avc_attack_opts* opts, avc_attack_opts* o) {
+    *o = avc_attack_opts{};
+    o->use_graph = 1;
+    if (opts) *o = *opts;
+    if (o->precision != AVC_PREC_FP32 && o->precision != AVC_PREC_BF16) return fail("bad precision %d", o->precision);
+    if (o->reduction != AVC_REDUCE_INDEPENDENT && o->reduction != AVC_REDUCE_MEAN)
+        return fail("bad reduction %d", o->reduction);
+    if (o->update != AVC_UPDATE_ADAM && !(o->update == AVC_UPDATE_PGD && o->pgd_step > 0.f))
+        return fail("bad update %d (PGD needs pgd_step > 0)", o->update);
+    return 0;
+}
+
+// the scalars of an attack call: [eps, loss-gradient scales g0 / g1, PGD step (0: Adam)]
+static int stage_attack_consts(avc_ctx* ctx, int n_iters, float eps, float g0, float g1, const avc_attack_opts& o) {
+    const float scal[4] = {eps, g0, g1, o.update == AVC_UPDATE_PGD ? o.pgd_step : 0.f};
+    return stage_call_consts(ctx, n_iters, scal);
+}
+
+// ptb <- ptb0, Adam state 0, adv = vc + eps*tanh(ptb), step counter 0
+static int attack_begin(avc_ctx* ctx, const float* ptb0, float eps, const avc_attack_opts& o) {
+    Workspace& ws = *ctx->cur;
+    hipLaunchKernelGGL(attack_init, dim3((unsigned)((ws.X + 255) / 256)), dim3(256), 0, ctx->stream, ws.vc.p, ptb0,
+                       ws.ptb.p, ws.m.p, ws.v.p, ws.adv.p, eps, ws.X, o.update == AVC_UPDATE_PGD ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(ws.step.get(), 0, sizeof(int), ctx->stream));
+    return 0;
+}
+
+// adv, and on request the loss rows and the first iteration's gradient, to the caller; ends the call
+static int attack_end(avc_ctx* ctx, int n_iters, float* out_adv, const avc_attack_opts& o, hipStream_t us) {
+    Workspace& ws = *ctx->cur;
+    if (d2d(ctx, out_adv, ws.adv.p, ws.X)) return 1;
+    if (o.losses && n_iters > 0 && d2d(ctx, o.losses, ws.losses.p, (size_t)n_iters * ws.B)) return 1;
+    if (o.grad0 && n_iters > 0 && d2d(ctx, o.grad0, ws.grad0.p, ws.X)) return 1;
+    return end_call(ctx, us);
 }
 
 // emb attack; the target embedding is SE(adv_tgt) at T frames (adv_tgt given) or the caller's
@@ -2062,85 +2121,32 @@ static int emb_attack_impl(avc_ctx* ctx, const float* vc_tgt, const float* adv_t
                            const avc_attack_opts* opts, void* stream, const std::vector<int>* lens = nullptr) {
     if (!ctx || !vc_tgt || !(adv_tgt || tgt_emb) || !ptb0 || !out_adv) return fail("avc_emb_attack: null argument");
     if (n_iters < 0) return fail("n_iters must be >= 0");
-    avc_attack_opts o{};
-    o.use_graph = 1;
-    if (opts) o = *opts;
-    if (o.precision != AVC_PREC_FP32 && o.precision != AVC_PREC_BF16) return fail("bad precision %d", o.precision);
-    if (o.reduction != AVC_REDUCE_INDEPENDENT && o.reduction != AVC_REDUCE_MEAN)
-        return fail("bad reduction %d", o.reduction);
-    if (o.update != AVC_UPDATE_ADAM && !(o.update == AVC_UPDATE_PGD && o.pgd_step > 0.f))
-        return fail("bad update %d (PGD needs pgd_step > 0)", o.update);
+    avc_attack_opts o;
+    if (attack_opts(opts, &o)) return 1;
     hipStream_t us = (hipStream_t)stream;
     if (ensure_ws(ctx, B, T, n_iters, lens)) return 1;
     Workspace& ws = *ctx->cur;
     const bool bf16 = o.precision == AVC_PREC_BF16;
-    if (bf16 && ws.iter_bf16.launches.empty()) {
-        // the setup below rewrites eps and the step counter with blocking copies on the null
+    if (bf16 && ws.pl.iter_bf16.launches.empty()) {
+        // the plan's set-up rewrites eps and the step counter with blocking copies on the null
         // stream: an earlier (asynchronous) call's loop on ctx->stream must be finished first
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (plan_iteration(ctx, ws, ws.iter_bf16, PREC_BF16)) return 1;
-        const float scal0[8] = {0.1f, 0.f, 0.f, 0.f, 0.1f, 0.f, 0.f, 0.f};
-        HIPCHK(hipMemcpy(ws.scal.p, scal0, sizeof(scal0), hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(ws.step, 0, sizeof(int)));
-        if (autotune(ctx, ws.iter_bf16)) return 1;
+        if (plan_tuned_iteration(ctx, ws, ws.pl.iter_bf16, PREC_BF16)) return 1;
     }
-    Plan& iter = bf16 ? ws.iter_bf16 : ws.iter;
-    hipGraphExec_t& graph = bf16 ? ws.graph_bf16 : ws.graph;
     if (begin_call(ctx, us)) return 1;
     const avc_se_cfg& c = ctx->cfg;
-    const size_t X = ws.X;   // B x 80 x T, or a ragged batch's packed sum
+    const size_t E = (size_t)B * c.c_out;
     const float gscale = (float)(2.0 / (o.reduction == AVC_REDUCE_MEAN ? (double)B * c.c_out : (double)c.c_out));
-
-    const float scal[4] = {eps, gscale, 0.f, o.update == AVC_UPDATE_PGD ? o.pgd_step : 0.f};
-    if (stage_call_consts(ctx, n_iters, scal)) return 1;
-    HIPCHK(hipMemcpyAsync(ws.vc.p, vc_tgt, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    if (stage_attack_consts(ctx, n_iters, eps, gscale, 0.f, o)) return 1;
     // org_emb = SE(vc_tgt), tgt_emb = SE(adv_tgt)   (attack_utils.py:73-75)
-    HIPCHK(hipMemcpyAsync(ws.xin.p, vc_tgt, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (run_plan(ctx, ws.fwd, false)) return 1;
-    HIPCHK(hipMemcpyAsync(ws.org.p, ws.emb_fwd.p, (size_t)B * c.c_out * sizeof(float), hipMemcpyDeviceToDevice,
-                          ctx->stream));
-    if (adv_tgt) {
-        HIPCHK(hipMemcpyAsync(ws.xin.p, adv_tgt, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        if (run_plan(ctx, ws.fwd, false)) return 1;
-    }
-    HIPCHK(hipMemcpyAsync(ws.tgt.p, adv_tgt ? ws.emb_fwd.p : tgt_emb, (size_t)B * c.c_out * sizeof(float),
-                          hipMemcpyDeviceToDevice, ctx->stream));
-    // ptb <- ptb0, Adam state 0, adv = vc + eps*tanh(ptb)
-    hipLaunchKernelGGL(attack_init, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, ctx->stream, ws.vc.p, ptb0,
-                       ws.ptb.p, ws.m.p, ws.v.p, ws.adv.p, eps, X, o.update == AVC_UPDATE_PGD ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ws.step, 0, sizeof(int), ctx->stream));
-
-    if (ctx->profiling) {
-        hipEvent_t a, b;
-        HIPCHK(hipEventCreate(&a));
-        HIPCHK(hipEventCreate(&b));
-        HIPCHK(hipEventRecord(a, ctx->stream));
-        for (int it = 0; it < n_iters; ++it)
-            if (run_plan(ctx, iter, true)) return 1;
-        HIPCHK(hipEventRecord(b, ctx->stream));
-        HIPCHK(hipEventSynchronize(b));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, a, b));
-        ctx->prof_iter_ms += ms;
-        ctx->prof_iters += n_iters;
-        hipEventDestroy(a);
-        hipEventDestroy(b);
-    } else if (persist_ok(iter)) {
-        if (run_persist(ctx, iter, n_iters)) return 1;
-    } else if (o.use_graph && n_iters > 0 && !(getenv("AVC_NO_GRAPH") && getenv("AVC_NO_GRAPH")[0] == '1')) {
-        if (graph_replay(ctx, iter, graph, n_iters)) return 1;
-    } else {
-        for (int it = 0; it < n_iters; ++it)
-            if (run_plan(ctx, iter, false)) return 1;
-    }
-    HIPCHK(hipMemcpyAsync(out_adv, ws.adv.p, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (o.losses && n_iters > 0)
-        HIPCHK(hipMemcpyAsync(o.losses, ws.losses.p, (size_t)n_iters * B * sizeof(float), hipMemcpyDeviceToDevice,
-                              ctx->stream));
-    if (o.grad0 && n_iters > 0)
-        HIPCHK(hipMemcpyAsync(o.grad0, ws.grad0.p, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    return end_call(ctx, us);
+    if (d2d(ctx, ws.vc.p, vc_tgt, ws.X) || se_embed(ctx, vc_tgt) || d2d(ctx, ws.org.p, ws.emb_fwd.p, E)) return 1;
+    if (adv_tgt && se_embed(ctx, adv_tgt)) return 1;
+    if (d2d(ctx, ws.tgt.p, adv_tgt ? ws.emb_fwd.p : tgt_emb, E)) return 1;
+    if (attack_begin(ctx, ptb0, eps, o)) return 1;
+    if (run_iterations(ctx, bf16 ? ws.pl.iter_bf16 : ws.pl.iter, bf16 ? ws.pl.graph_bf16 : ws.pl.graph, n_iters,
+                       o.use_graph != 0))
+        return 1;
+    return attack_end(ctx, n_iters, out_adv, o, us);
 }
 
 extern "C" int avc_emb_attack(avc_ctx* ctx, const float* vc_tgt, const float* adv_tgt, const float* ptb0, int B,
@@ -2171,8 +2177,6 @@ extern "C" int avc_emb_attack_ragged(avc_ctx* ctx, const float* vc_tgt, const in
     return emb_attack_impl(ctx, vc_tgt, nullptr, tgt_emb, ptb0, B, 0, eps, n_iters, out_adv, opts, stream, &lens);
 }
 
-static int run_iterations(avc_ctx* ctx, Plan& iter, hipGraphExec_t& graph, int n_iters, bool use_graph);
-
 // UniversalPerturbationHeader.optimize (models/header_model.py:25-68) driven as
 // train_header.py:46,77-80 does (torch Adam on the header): per iteration one captured graph
 // of  hdr_compose -> SpeakerEncoder forward (+ loss, head backward) -> input-gradient pass
@@ -2191,7 +2195,7 @@ static int plan_header(avc_ctx* ctx, Workspace& ws, Plan& pl, int prec, int N, i
     H.x = ws.adv.p;
     H.gx = ws.hdr_gx.p;
     H.table = ws.table.p;
-    H.step = ws.step;
+    H.step = ws.step.get();
     H.table_len = ws.iters_cap;
     H.N = N;
     H.FT = FT;
@@ -2236,7 +2240,7 @@ static int header_optimize_impl(avc_ctx* ctx, const float* source, const float* 
     int rc = dalloc(ws.hdr, FT) | dalloc(ws.hdr_m, FT) | dalloc(ws.hdr_v, FT) | dalloc(ws.hdr_gx, X);
     if (rc) return 1;
     const int p = precision == AVC_PREC_BF16 ? 1 : 0;
-    Plan& pl = ws.hdr_it[p];
+    Plan& pl = ws.pl.hdr_it[p];
     if (pl.launches.empty()) {
         HIPCHK(hipStreamSynchronize(ctx->stream));
         if (plan_header(ctx, ws, pl, p ? PREC_BF16 : PREC_F32, N, FT)) return 1;
@@ -2249,43 +2253,27 @@ static int header_optimize_impl(avc_ctx* ctx, const float* source, const float* 
             L.hd.adam_eps = adam_eps;
             L.hd.clamp_eps = epsilon;
         }
-    hipGraphExec_t& graph = ws.hdr_graph[p];
-    if (graph) {   // the Adam / clamp constants live in the kernel arguments: re-capture
-        (void)hipGraphExecDestroy(graph);
-        graph = nullptr;
-    }
+    GraphExec& graph = ws.pl.hdr_graph[p];
+    graph.reset();   // the Adam / clamp constants live in the kernel arguments: re-capture
     if (begin_call(ctx, us)) return 1;
     const float gscale = (float)(2.0 / ((double)N * c.c_out));
     const float scal[4] = {epsilon, gscale, 0.f, 0.f};
     if (stage_call_consts(ctx, n_iters, scal, lr, beta1, beta2, lambda_param, step0)) return 1;
     // source_embedding = SE(source), target_embedding = SE(target)   (header_model.py:48-49)
-    HIPCHK(hipMemcpyAsync(ws.vc.p, source, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ws.xin.p, source, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (run_plan(ctx, ws.fwd, false)) return 1;
-    HIPCHK(hipMemcpyAsync(ws.org.p, ws.emb_fwd.p, (size_t)N * c.c_out * sizeof(float), hipMemcpyDeviceToDevice,
-                          ctx->stream));
-    HIPCHK(hipMemcpyAsync(ws.xin.p, target, X * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (run_plan(ctx, ws.fwd, false)) return 1;
-    HIPCHK(hipMemcpyAsync(ws.tgt.p, ws.emb_fwd.p, (size_t)N * c.c_out * sizeof(float), hipMemcpyDeviceToDevice,
-                          ctx->stream));
-    HIPCHK(hipMemcpyAsync(ws.hdr.p, header, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    const size_t E = (size_t)N * c.c_out;
+    if (d2d(ctx, ws.vc.p, source, X) || se_embed(ctx, source) || d2d(ctx, ws.org.p, ws.emb_fwd.p, E)) return 1;
+    if (se_embed(ctx, target) || d2d(ctx, ws.tgt.p, ws.emb_fwd.p, E) || d2d(ctx, ws.hdr.p, header, FT)) return 1;
     if (exp_avg) {   // the caller's optimiser state (torch Adam exp_avg / exp_avg_sq)
-        HIPCHK(hipMemcpyAsync(ws.hdr_m.p, exp_avg, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ws.hdr_v.p, exp_avg_sq, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        if (d2d(ctx, ws.hdr_m.p, exp_avg, FT) || d2d(ctx, ws.hdr_v.p, exp_avg_sq, FT)) return 1;
     } else {
         HIPCHK(hipMemsetAsync(ws.hdr_m.p, 0, FT * sizeof(float), ctx->stream));
         HIPCHK(hipMemsetAsync(ws.hdr_v.p, 0, FT * sizeof(float), ctx->stream));
     }
-    HIPCHK(hipMemsetAsync(ws.step, 0, sizeof(int), ctx->stream));
+    HIPCHK(hipMemsetAsync(ws.step.get(), 0, sizeof(int), ctx->stream));
     if (run_iterations(ctx, pl, graph, n_iters, true)) return 1;
-    HIPCHK(hipMemcpyAsync(header, ws.hdr.p, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    if (exp_avg) {
-        HIPCHK(hipMemcpyAsync(exp_avg, ws.hdr_m.p, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(exp_avg_sq, ws.hdr_v.p, FT * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (losses && n_iters > 0)
-        HIPCHK(hipMemcpyAsync(losses, ws.losses.p, (size_t)n_iters * N * sizeof(float), hipMemcpyDeviceToDevice,
-                              ctx->stream));
+    if (d2d(ctx, header, ws.hdr.p, FT)) return 1;
+    if (exp_avg && (d2d(ctx, exp_avg, ws.hdr_m.p, FT) || d2d(ctx, exp_avg_sq, ws.hdr_v.p, FT))) return 1;
+    if (losses && n_iters > 0 && d2d(ctx, losses, ws.losses.p, (size_t)n_iters * N)) return 1;
     return end_call(ctx, us);
 }
 
@@ -2323,14 +2311,14 @@ extern "C" int avc_ws_stats(avc_ctx* ctx, int64_t* builds, int64_t* replans, int
     if (replans) *replans = ctx->n_ws_replans;
     if (hits) *hits = ctx->n_ws_hits;
     if (captures) *captures = ctx->n_graph_captures;
-    if (evictions) *evictions = ctx->n_ws_evictions;
+    if (evictions) *evictions = ctx->wss.evictions + ctx->n_vc_evictions + vc_evictions(ctx);
     return 0;
 }
 
 extern "C" int avc_set_ws_cache(avc_ctx* ctx, int n_shapes) {
     if (!ctx) return fail("null ctx");
     if (n_shapes < 1 || n_shapes > 64) return fail("avc_set_ws_cache: n_shapes must be in [1, 64] (got %d)", n_shapes);
-    ctx->ws_cap = n_shapes;
+    ctx->wss.cap = n_shapes;   // (the VC cache takes it over in ensure_vc_ws)
     return 0;
 }
 

@@ -376,10 +376,7 @@ extern "C" int avc_dsp_create(int device, const avc_dsp_cfg* cfg, avc_dsp** out)
 
 extern "C" void avc_dsp_destroy(avc_dsp* d) {
     if (!d) return;
-    for (DevBuf* b : {&d->window, &d->twiddle, &d->mel_basis, &d->mel_range, &d->inv_mel, &d->spect, &d->frames, &d->y, &d->wss,
-                      &d->tprev})
-        dfree(*b);
-    delete d;
+    delete d;   // its buffers free themselves
 }
 
 extern "C" int avc_dsp_wav2mel(avc_dsp* d, const float* wav, int B, int L, const float* mean, const float* std_,

@@ -155,16 +155,7 @@ extern "C" int avc_pm_create(int device, const float* w, size_t n, avc_pm** out)
 extern "C" void avc_pm_destroy(avc_pm* pm) {
     if (!pm) return;
     hipSetDevice(pm->device);
-    for (auto& L : pm->layers) {
-        dfree(L.w);
-        dfree(L.b);
-        dfree(L.wm);
-    }
-    for (auto& b : pm->act) dfree(b);
-    dfree(pm->part);
-    dfree(pm->vwin);
-    dfree(pm->vy);
-    delete pm;
+    delete pm;   // its buffers free themselves
 }
 
 // one layer: y = layer(x) over B windows of Hin x Win (the layer's input); layouts NCHW / NHWC as
@@ -205,11 +196,11 @@ static int pm_layer(avc_pm* pm, int l, const float* x, int B, int Hin, int Win, 
     // window geometry only, never from B, so a window's summation order (and result) is the same
     // in any batch: pm_conv -- ~256 workgroups at B = 1, >= 8 K chunks of 16 per slice; pm_mfma --
     // >= 256 workgroups at a reference batch of 128 windows, >= 8 K chunks per slice
-    const int MT = L.Cout >= 64 && !(getenv("AVC_PM_MT") && getenv("AVC_PM_MT")[0] == '2') ? 4 : 2;
+    const int MT = L.Cout >= 64 && !env_is("AVC_PM_MT", '2') ? 4 : 2;
     // N tiles of 16 output pixels per wave (MT = 4 layers): the workgroup covers 64 * NT pixels
     // (A/B, B = 256, MT = 4 layers: NT = 1 310k windows/s, 2 292k, 4 251k -- the smaller tiles balance
     // the CUs and leave registers for 5 waves per SIMD; the MT = 2 layer: NT = 2 50 us, NT = 1 54 us)
-    const int nt_env = getenv("AVC_PM_NT") ? atoi(getenv("AVC_PM_NT")) : 0;
+    const int nt_env = env_int("AVC_PM_NT", 0);
     const int NT = nt_env == 1 || nt_env == 2 || (nt_env == 4 && MT == 4) ? nt_env : (MT == 4 ? 1 : 2);
     const long wgs = mfma ? ((128 * N1 + 127) / 128) * ((L.Cout + 16 * MT - 1) / (16 * MT)) * ncls
                           : ((N1 + 63) / 64) * ((L.Cout + 63) / 64) * ncls;
@@ -217,7 +208,7 @@ static int pm_layer(avc_pm* pm, int l, const float* x, int B, int Hin, int Win, 
     int ksplit = 1;
     // (the pm_mfma target, workgroups at the reference batch; A/B at B = 256: 64 -> 286k windows/s,
     // 128 -> 308k, 256 -> 310k, 512 -> 296k)
-    const long ks_target = getenv("AVC_PM_KSWG") ? atol(getenv("AVC_PM_KSWG")) : 256;
+    const long ks_target = env_int("AVC_PM_KSWG", 256);
     if (mfma)
         while (wgs * ksplit < ks_target && kchunks >= 16 * ksplit) ksplit *= 2;
     else
@@ -225,7 +216,7 @@ static int pm_layer(avc_pm* pm, int l, const float* x, int B, int Hin, int Win, 
     const size_t per = (size_t)B * L.Cout * P.Ho * P.Wo;
     // the edge layers on their own kernels (pm_conv's per-output arithmetic, bitwise): Cin = 1 into
     // NHWC, and Cout = 1 (its K slices summed in-thread in pm_reduce's order).  AVC_PM_EDGE=0: pm_conv
-    const bool edge = !(getenv("AVC_PM_EDGE") && getenv("AVC_PM_EDGE")[0] == '0');
+    const bool edge = !env_is("AVC_PM_EDGE", '0');
     if (edge && !mfma && L.mode == 0 && L.Cin == 1 && L.Cout == 32 && out_nhwc && ksplit == 1) {
         hipLaunchKernelGGL(pm_cin1<32>, dim3((unsigned)((B * (long)P.Ho * P.Wo + 255) / 256)), dim3(256), 0, s, P);
         HIPCHK(hipGetLastError());
@@ -234,7 +225,7 @@ static int pm_layer(avc_pm* pm, int l, const float* x, int B, int Hin, int Win, 
     if (edge && !mfma && L.mode == 1 && L.Cout == 1 && in_nhwc && L.Cin == 32) {
         P.ksplit = ksplit;
         // ksplit 2 on CI = 32 splits every class at ci = 16: the half-channel kernel (same bits)
-        const bool halves = ksplit == 2 && !(getenv("AVC_PM_COUT1H") && getenv("AVC_PM_COUT1H")[0] == '0');
+        const bool halves = ksplit == 2 && !env_is("AVC_PM_COUT1H", '0');
         if (halves) hipLaunchKernelGGL(pm_cout1h<32>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, P);
         else hipLaunchKernelGGL(pm_cout1<32>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, P);
         HIPCHK(hipGetLastError());
@@ -290,8 +281,7 @@ extern "C" int avc_pm_forward(avc_pm* pm, const float* x, int B, int H, int W, f
     hipStream_t s = (hipStream_t)stream;
     // NHWC between layers (the matrix-core layers' layout); the network's own input and output
     // have one channel, so NCHW == NHWC there.  AVC_PM_MFMA=0: every layer on pm_conv (A/B runs).
-    const char* e = getenv("AVC_PM_MFMA");
-    const bool mfma = !(e && e[0] == '0');
+    const bool mfma = !env_is("AVC_PM_MFMA", '0');
     const float* in = x;
     for (int l = 0; l < nl; ++l) {
         float* out = l + 1 < nl ? pm->act[l].p : y;

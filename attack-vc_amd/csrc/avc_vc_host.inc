@@ -17,16 +17,17 @@ struct VcWs {
     DevBuf src, mu, emb, cond, gcond, gemb, stash, invstd, out, tgt_out, org_out, gout, gdec, pooled2, gpooled2;
     DevBuf lsig;                          // ContentEncoder.forward's log_sigma (std_layer), on demand
     DevBuf hact;                          // fused head: SE(adv)'s dense activations [B][2nd][C] (mode 0 -> 3)
-    unsigned long long* masks2 = nullptr;
+    DevPtr<unsigned long long> masks2;
     bool ce_long = false, dec_long = false, se2_long = false;   // long engine for these lengths
-    LongArgs lz{};                        // their scratch (max(Ts, Tn) frames) + SE2's ballot masks
+    LongScratch lz;                       // their scratch (max(Ts, Tn) frames) + SE2's ballot masks
     int stash_per_utt = 0;
     std::vector<int> stash_off;
-    Plan ce, ce_std, dec_pre, se2_pre;
-    Plan it[2][2];                        // [e2e | fb][PREC]
-    hipGraphExec_t graph[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     int ws_gen = -1;                      // SpeakerEncoder workspace generation the plans point into
-    bool built = false;
+    struct Plans {                        // rebuilt whenever the SpeakerEncoder workspace is re-planned (renew)
+        Plan ce, ce_std, dec_pre, se2_pre;
+        Plan it[2][2];                    // [e2e | fb][PREC]
+        GraphExec graph[2][2];
+    } pl;                                 // last: destroyed before the buffers its launches point into
 };
 
 }  // namespace
@@ -46,54 +47,20 @@ struct VcState {
     std::vector<SnChunk> sn_chunks[2];
     DevBuf sn_raw, sn_uv, sn_sigma, sn_layer_dev, sn_chunk_dev[2], sn_train;   // sn_train: 1 int (SnArgs.train)
     size_t sn_uv_count = 0;
-    // per-shape workspaces (B, T, Ts), most recently used first; each one's plans point into the
-    // SpeakerEncoder workspace whose gen they record (ws_gen)
-    std::list<VcWs> wss;
+    // workspaces by VcKey {B, T, Ts, ce_long, dec_long}, most recently used first; each one's plans
+    // point into the SpeakerEncoder workspace whose gen they record (ws_gen)
+    LruCache<VcKey, VcWs> wss;
     VcWs* cur = nullptr;
 };
 
-static void vc_free_plans(VcWs& v) {
-    for (auto& g : v.graph)
-        for (auto& e : g) {
-            if (e) (void)hipGraphExecDestroy(e);
-            e = nullptr;
-        }
-    free_plan(v.ce);
-    free_plan(v.ce_std);
-    free_plan(v.dec_pre);
-    free_plan(v.se2_pre);
-    for (auto& a : v.it)
-        for (auto& p : a) free_plan(p);
-}
-
-static void vc_free_ws(VcWs& v) {
-    vc_free_plans(v);
-    for (DevBuf* b : {&v.src, &v.mu, &v.emb, &v.cond, &v.gcond, &v.gemb, &v.stash, &v.invstd, &v.out, &v.tgt_out,
-                      &v.org_out, &v.gout, &v.gdec, &v.pooled2, &v.gpooled2, &v.hact, &v.lsig})
-        dfree(*b);
-    if (v.masks2) (void)hipFree(v.masks2);
-    v.masks2 = nullptr;
-    if (v.lz.img[0]) (void)hipFree(v.lz.img[0]);
-    if (v.lz.fl[0]) (void)hipFree(v.lz.fl[0]);
-    if (v.lz.masks) (void)hipFree(v.lz.masks);
-    v.lz = LongArgs{};
-    v.built = false;
-    v.B = v.T = v.Ts = 0;
-}
-
+// (callers have the device current and the stream drained)
 static void vc_free(avc_ctx* ctx) {
     if (!ctx->vc) return;
-    for (VcWs& w : ctx->vc->wss) vc_free_ws(w);
-    ctx->vc->wss.clear();
-    ctx->vc->cur = nullptr;
-    for (DevBuf* b : {&ctx->vc->aff, &ctx->vc->affT, &ctx->vc->aff_b, &ctx->vc->sn_raw, &ctx->vc->sn_uv,
-                      &ctx->vc->sn_sigma, &ctx->vc->sn_layer_dev, &ctx->vc->sn_chunk_dev[0], &ctx->vc->sn_chunk_dev[1],
-                      &ctx->vc->sn_train})
-        dfree(*b);
-    for (auto& b : ctx->vc->own) dfree(b);
+    ctx->n_vc_evictions += ctx->vc->wss.evictions;
     delete ctx->vc;
     ctx->vc = nullptr;
 }
+static long vc_evictions(avc_ctx* ctx) { return ctx->vc ? ctx->vc->wss.evictions : 0; }
 
 static avc_se_cfg ce_as_encoder(const avc_vc_cfg& v) {
     avc_se_cfg c{};
@@ -163,6 +130,8 @@ extern "C" int avc_attach_vc(avc_ctx* ctx, const avc_vc_cfg* cfgp, const float* 
     vc_free(ctx);
     VcState* S = new VcState();
     ctx->vc = S;
+    S->wss.tag = "vc";
+    S->wss.trace = debug_ws();
     S->cfg = v;
     S->ce = ce_as_encoder(v);
     const avc_se_cfg& ce = S->ce;
@@ -476,30 +445,11 @@ extern "C" int avc_vc_out_frames(avc_ctx* ctx, int T) {
     return Tn;
 }
 
-static int enc_shape(const avc_se_cfg& c, int nb, int T) {
-    bool std_cfg = T == 128 && nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
-    for (int l = 0; std_cfg && l < 6; ++l)
-        if (c.subsample[l] != ((l & 1) ? 2 : 1)) std_cfg = false;
-    const char* e = getenv("AVC_FUSED_STD");
-    const char* rf = getenv("AVC_FUSED_RT_FORCE");   // A/B runs: the runtime-length kernels at T = 128 too
-    if (std_cfg && rf && rf[0] == '1') return 16;
-    if (std_cfg && !(e && e[0] == '0')) return 0;
-    // 64 < T < 128: the standard classes with runtime lengths (avc_api.hip fused_shape)
-    bool std_rt = T > 64 && T < 128 && nb == 8 && c.kernel_size == 5 && c.n_conv_blocks == 6 && c.act == 0;
-    for (int l = 0; std_rt && l < 6; ++l)
-        if (c.subsample[l] != ((l & 1) ? 2 : 1)) std_rt = false;
-    const char* r = getenv("AVC_FUSED_RT");
-    if (std_rt && !(e && e[0] == '0') && !(r && r[0] == '0')) return 16;
-    const int nf = cdiv(T, 16);
-    return nf <= 1 ? 1 : nf <= 2 ? 2 : nf <= 4 ? 4 : 8;
-}
-
 static int dec_shape(const avc_vc_cfg& v, int T0) {
     bool std_cfg = T0 == 16 && v.dec_n_conv_blocks == 6 && v.dec_kernel_size == 5 && v.dec_act == 0;
     for (int l = 0; std_cfg && l < 6; ++l)
         if (v.dec_upsample[l] != ((l & 1) ? 1 : 2)) std_cfg = false;
-    const char* e = getenv("AVC_FUSED_STD");
-    return (std_cfg && !(e && e[0] == '0')) ? 0 : 8;
+    return (std_cfg && !env_is("AVC_FUSED_STD", '0')) ? 0 : 8;
 }
 
 static FusedArgs enc_args(const avc_se_cfg& c, int nb, int B, const std::vector<int>& Tl, const FusedW& w) {
@@ -651,7 +601,7 @@ static Launch dec_launch(avc_ctx* ctx, int kind, int prec, int B, const std::vec
     if (w.dec_long) {
         L.kind = kind == L_DZ_FWD ? L_LZD_FWD : L_LZD_BWD;
         L.shmem = LZ_SHMEM;
-        L.lz = w.lz;
+        L.lz = w.lz.a;
     }
     DecArgs& A = L.dz;
     A.B = B;
@@ -675,120 +625,104 @@ static Launch dec_launch(avc_ctx* ctx, int kind, int prec, int B, const std::vec
     return L;
 }
 
-// a VC workspace whose build failed part-way: release it and forget it (returns 1), so no
-// unbuilt entry keeps device memory at the head of the cache
-static int drop_vc_ws(avc_ctx* ctx) {
-    VcState* S = ctx->vc;
-    for (auto it = S->wss.begin(); it != S->wss.end(); ++it)
-        if (&*it == S->cur) {
-            (void)hipStreamSynchronize(ctx->stream);
-            vc_free_ws(*it);
-            S->wss.erase(it);
-            break;
-        }
-    S->cur = nullptr;
+// a VC workspace whose build or plan failed part-way: forget it (its owners free what it holds); returns 1
+static int drop_vc_cur(avc_ctx* ctx) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->vc->wss.erase(ctx->vc->cur);
+    ctx->vc->cur = nullptr;
     return 1;
 }
 
+// the lengths and buffers of a new VC workspace for key `k` over the SpeakerEncoder workspace `ws`
+static int build_vc_ws(avc_ctx* ctx, VcWs& w, const VcKey& k, const Workspace& ws) {
+    VcState* S = ctx->vc;
+    const avc_se_cfg& c = ctx->cfg;
+    const avc_vc_cfg& v = S->cfg;
+    if (enc_lengths(S->ce, S->ce_bank_k, k.Ts, w.Tl_ce) || dec_lengths(v, w.Tl_ce.back(), w.Tl_dec)) return 1;
+    w.Tce = w.Tl_ce.back();
+    w.Tn = w.Tl_dec.back();
+    if (enc_lengths(c, ctx->bank_k, w.Tn, w.Tl_se2)) return 1;
+    w.B = k.B;
+    w.T = k.T;
+    w.Ts = k.Ts;
+    const int nd = v.dec_n_conv_blocks;
+    // long engine for lengths past the fused engine's 128 frames (or when forced: then all three)
+    w.ce_long = k.ce_long;
+    w.dec_long = k.dec_long;
+    w.se2_long = (k.ce_long && k.Ts <= 128) || w.Tn > 128;
+    w.stash_off.assign(2 * DZ_MAXBLK, 0);
+    int off = 0;
+    for (int l = 0; l < nd; ++l) {
+        // fused: [half][fragment] per layer; long: the fragment-layout stream of the layer's frames
+        const int nfq = cdiv(w.Tl_dec[l], 16), nfo = cdiv(w.Tl_dec[l + 1], 16);
+        w.stash_off[2 * l] = off;
+        off += 2048 * nfq;
+        w.stash_off[2 * l + 1] = off;
+        off += 2048 * (w.dec_long ? nfo : nfq * v.dec_upsample[l]);
+    }
+    w.stash_per_utt = off;
+    const size_t Bz = k.B;
+    int rc = 0;
+    rc |= dalloc(w.src, Bz * FZ_CIN * k.Ts);
+    rc |= dalloc(w.mu, Bz * FZ_C * w.Tce);
+    rc |= dalloc(w.lsig, Bz * FZ_C * w.Tce);
+    for (DevBuf* b : {&w.emb, &w.pooled2, &w.gpooled2}) rc |= dalloc(*b, Bz * FZ_C);
+    rc |= dalloc(w.gemb, Bz * FZ_C * 4 * nd);   // split-K slices of d loss / d emb
+    rc |= dalloc(w.hact, Bz * 2 * c.n_dense_blocks * FZ_C);
+    rc |= dalloc(w.cond, Bz * 2 * nd * 2 * FZ_C);
+    rc |= dalloc(w.gcond, Bz * 2 * nd * 2 * FZ_C);
+    rc |= dalloc(w.stash, Bz * (size_t)w.stash_per_utt);
+    rc |= dalloc(w.invstd, Bz * 2 * nd * FZ_C);
+    for (DevBuf* b : {&w.out, &w.tgt_out, &w.org_out, &w.gout, &w.gdec}) rc |= dalloc(*b, Bz * DZ_COUT * w.Tn);
+    if (rc || dmalloc(w.masks2, Bz * ws.mask_words * sizeof(unsigned long long))) return 1;
+    return (w.ce_long || w.dec_long || w.se2_long) &&
+           alloc_long(w.lz, k.B, std::max(k.Ts, w.Tn), (int)ctx->bank_k.size() + 1 + 2 * c.n_conv_blocks);
+}
+
+static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws);
+
+// The VC workspace of a call (ctx->vc->cur) over the SpeakerEncoder workspace of (B, T): resolve the
+// key, look it up, build a new entry or re-plan one whose SpeakerEncoder workspace was re-planned, plan.
 static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
     VcState* S = ctx->vc;
     if (!S) return fail("no ContentEncoder/Decoder attached (avc_attach_vc)");
     if (ensure_ws(ctx, B, T, n_iters)) return 1;
     Workspace& ws = *ctx->cur;
     if (!ws.fused) return fail("the e2e / fb path runs on the fused engine only (T <= 128, engine not LAYERED)");
-    // the engine of each component is part of the shape (avc_set_engine may force the long one)
+    // the engine of each component is part of the key (avc_set_engine may force the long one)
     std::vector<int> tce, tdec;
     if (enc_lengths(S->ce, S->ce_bank_k, Ts, tce) || dec_lengths(S->cfg, tce.back(), tdec)) return 1;
-    const int eng = engine_for(ctx, std::max(Ts, tdec.back()));
-    const bool force = eng == AVC_ENGINE_LONG && std::max(Ts, tdec.back()) <= 128;
-    const bool ce_long = force || Ts > 128, dec_long = force || tdec.back() > 128;
-    auto it = S->wss.begin();
-    for (; it != S->wss.end(); ++it)
-        if (it->built && it->B == B && it->T == T && it->Ts == Ts && it->ce_long == ce_long && it->dec_long == dec_long)
-            break;
-    static const bool dbg_ws = getenv("AVC_DEBUG_WS") && getenv("AVC_DEBUG_WS")[0] == '1';
-    if (dbg_ws)
-        fprintf(stderr, "AVC_DEBUG_WS ensure_vc_ws B=%d T=%d Ts=%d ce_long=%d dec_long=%d ws.gen=%d: %s (%zu cached)\n", B, T,
-                Ts, (int)ce_long, (int)dec_long, ws.gen, it != S->wss.end() ? "hit" : "new", S->wss.size());
-    const bool found = it != S->wss.end();
-    if (found) {
-        S->wss.splice(S->wss.begin(), S->wss, it);
-    } else {
-        const char* ce = getenv("AVC_WS_CACHE");
-        const int cap = std::max(1, ce ? atoi(ce) : ctx->ws_cap);
-        while ((int)S->wss.size() >= cap) {
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (dbg_ws)
-                fprintf(stderr, "AVC_DEBUG_WS evict vc B=%d T=%d Ts=%d gen=%d\n", S->wss.back().B, S->wss.back().T,
-                        S->wss.back().Ts, S->wss.back().ws_gen);
-            vc_free_ws(S->wss.back());
-            S->wss.pop_back();
-            ++ctx->n_ws_evictions;
-        }
-        S->wss.emplace_front();
-        ++ctx->n_ws_builds;
-    }
-    S->cur = &S->wss.front();
-    VcWs& w = *S->cur;
-    if (w.built && w.ws_gen == ws.gen) {
+    const int Tmax = std::max(Ts, tdec.back());
+    const bool force = engine_for(ctx, Tmax) == AVC_ENGINE_LONG && Tmax <= 128;
+    const VcKey k{B, T, Ts, force || Ts > 128, force || tdec.back() > 128};
+    S->cur = S->wss.find(k);
+    if (S->cur && S->cur->ws_gen == ws.gen) {
         ++ctx->n_ws_hits;               // served by the cached workspace as it was (include/avc.h "hits")
         return 0;
     }
-    if (w.built) ++ctx->n_ws_replans;   // found, but the SpeakerEncoder workspace under it was re-planned
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        fail("hipStreamSynchronize failed");
-        return drop_vc_ws(ctx);
+    const bool fresh = !S->cur;
+    auto quiesce = [&] { return hipStreamSynchronize(ctx->stream) != hipSuccess; };
+    if (fresh) {
+        S->wss.cap = ctx->wss.cap;
+        S->cur = S->wss.insert(k, env_int("AVC_WS_CACHE", S->wss.cap), quiesce);
+        if (!S->cur) return fail("hipStreamSynchronize failed before a workspace eviction");
     }
+    ++(fresh ? ctx->n_ws_builds : ctx->n_ws_replans);   // (replan: the SpeakerEncoder workspace under it was)
+    if (quiesce()) {
+        fail("hipStreamSynchronize failed");
+        return drop_vc_cur(ctx);
+    }
+    if ((fresh && build_vc_ws(ctx, *S->cur, k, ws)) || plan_vc_ws(ctx, *S->cur, ws)) return drop_vc_cur(ctx);
+    return 0;
+}
+
+// every plan of `w`, pointing into `ws` as it is now
+static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
+    VcState* S = ctx->vc;
     const avc_se_cfg& c = ctx->cfg;
     const avc_vc_cfg& v = S->cfg;
-    if (!(w.built && w.B == B && w.T == T && w.Ts == Ts && w.ce_long == ce_long && w.dec_long == dec_long)) {
-        vc_free_ws(w);
-        if (enc_lengths(S->ce, S->ce_bank_k, Ts, w.Tl_ce) || dec_lengths(v, w.Tl_ce.back(), w.Tl_dec)) return drop_vc_ws(ctx);
-        w.Tce = w.Tl_ce.back();
-        w.Tn = w.Tl_dec.back();
-        if (enc_lengths(c, ctx->bank_k, w.Tn, w.Tl_se2)) return drop_vc_ws(ctx);
-        w.B = B;
-        w.T = T;
-        w.Ts = Ts;
-        const int nd = v.dec_n_conv_blocks;
-        // long engine for lengths past the fused engine's 128 frames (or when forced)
-        w.ce_long = ce_long;
-        w.dec_long = dec_long;
-        w.se2_long = force || w.Tn > 128;
-        w.stash_off.assign(2 * DZ_MAXBLK, 0);
-        int off = 0;
-        for (int l = 0; l < nd; ++l) {
-            // fused: [half][fragment] per layer; long: the fragment-layout stream of the layer's frames
-            const int nfq = cdiv(w.Tl_dec[l], 16), nfo = cdiv(w.Tl_dec[l + 1], 16);
-            w.stash_off[2 * l] = off;
-            off += 2048 * nfq;
-            w.stash_off[2 * l + 1] = off;
-            off += 2048 * (w.dec_long ? nfo : nfq * v.dec_upsample[l]);
-        }
-        w.stash_per_utt = off;
-        const size_t Bz = B;
-        int rc = 0;
-        rc |= dalloc(w.src, Bz * FZ_CIN * Ts);
-        rc |= dalloc(w.mu, Bz * FZ_C * w.Tce);
-        rc |= dalloc(w.lsig, Bz * FZ_C * w.Tce);
-        for (DevBuf* b : {&w.emb, &w.pooled2, &w.gpooled2}) rc |= dalloc(*b, Bz * FZ_C);
-        rc |= dalloc(w.gemb, Bz * FZ_C * 4 * nd);   // split-K slices of d loss / d emb
-        rc |= dalloc(w.hact, Bz * 2 * c.n_dense_blocks * FZ_C);
-        rc |= dalloc(w.cond, Bz * 2 * nd * 2 * FZ_C);
-        rc |= dalloc(w.gcond, Bz * 2 * nd * 2 * FZ_C);
-        rc |= dalloc(w.stash, Bz * (size_t)w.stash_per_utt);
-        rc |= dalloc(w.invstd, Bz * 2 * nd * FZ_C);
-        for (DevBuf* b : {&w.out, &w.tgt_out, &w.org_out, &w.gout, &w.gdec}) rc |= dalloc(*b, Bz * DZ_COUT * w.Tn);
-        if (rc) return drop_vc_ws(ctx);
-        if (hipMalloc(&w.masks2, Bz * ws.mask_words * sizeof(unsigned long long)) != hipSuccess) {
-            fail("hipMalloc(masks2) failed");
-            return drop_vc_ws(ctx);
-        }
-        if ((w.ce_long || w.dec_long || w.se2_long) &&
-            alloc_long(w.lz, B, std::max(Ts, w.Tn), (int)ctx->bank_k.size() + 1 + 2 * c.n_conv_blocks))
-            return drop_vc_ws(ctx);
-    }
-    vc_free_plans(w);
+    const int B = w.B, T = w.T, Ts = w.Ts;
+    renew(w.pl);
     const int nbS = ctx->nb, nbC = (int)S->ce_bank_k.size();
     const int nd = v.dec_n_conv_blocks, M = 2 * nd * 2 * FZ_C;
     const double se_fl = fz_fwd_flop(c, ws.Tl, ctx->bank_k) * B;
@@ -801,53 +735,52 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
         A.x = w.src.p;
         A.ce_mode = 1;
         A.mu_out = w.mu.p;
-        w.ce.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, enc_shape(S->ce, nbC, Ts), S->ce.kernel_size,
+        w.pl.ce.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, enc_shape(S->ce, nbC, Ts), S->ce.kernel_size,
                                            fz_fwd_flop(S->ce, w.Tl_ce, S->ce_bank_k) * B, "ce",
-                                           w.ce_long ? &w.lz : nullptr));
-        w.ce.launches.back().name = w.ce_long ? "lz_ce_fwd<f32>" : "ce_fwd_fused<f32>";
+                                           w.ce_long ? &w.lz.a : nullptr));
+        w.pl.ce.launches.back().name = w.ce_long ? "lz_ce_fwd<f32>" : "ce_fwd_fused<f32>";
         // log_sigma = std_layer(h_N): the same pass with std_layer as the final 1x1 (on demand)
         A.w = S->cew_std[PREC_F32];
         A.mu_out = w.lsig.p;
-        w.ce_std.launches.push_back(w.ce.launches.back());
-        w.ce_std.launches.back().fz = A;
+        w.pl.ce_std.launches.push_back(w.pl.ce.launches.back());
+        w.pl.ce_std.launches.back().fz = A;
     }
     // Decoder(mu, emb = ws.emb_fwd) -> w.out (fp32, precomputations / inference)
-    sn_launches(ctx, PREC_F32, w.dec_pre);
-    w.dec_pre.launches.push_back(dense_launch(S->aff.p, ws.emb_fwd.p, S->aff_b.p, w.cond.p, M, FZ_C, B, "dense_affine"));
-    w.dec_pre.launches.push_back(dec_launch(ctx, L_DZ_FWD, PREC_F32, B, w.Tl_dec, false));
+    sn_launches(ctx, PREC_F32, w.pl.dec_pre);
+    w.pl.dec_pre.launches.push_back(dense_launch(S->aff.p, ws.emb_fwd.p, S->aff_b.p, w.cond.p, M, FZ_C, B, "dense_affine"));
+    w.pl.dec_pre.launches.push_back(dec_launch(ctx, L_DZ_FWD, PREC_F32, B, w.Tl_dec, false));
     {   // SpeakerEncoder(w.out) -> ws.emb_fwd (fp32; fb's org embedding)
         FusedArgs A = enc_args(c, nbS, B, w.Tl_se2, ctx->fzw[PREC_F32]);
         A.x = w.out.p;
         A.pooled = w.pooled2.p;
-        A.masks = w.masks2;
+        A.masks = w.masks2.get();
         A.mask_words = ws.mask_words;
-        w.se2_pre.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, shS2, c.kernel_size, se2_fl, "se2",
-                                                w.se2_long ? &w.lz : nullptr));
-        w.se2_pre.launches.push_back(head_launch(ctx, B, TNs2, 0, w.pooled2.p, nullptr, ws.emb_fwd.p, nullptr, nullptr,
-                                                 nullptr, ws.step, ws.scal.p, ws.iters_cap, PREC_F32));
+        w.pl.se2_pre.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, shS2, c.kernel_size, se2_fl, "se2",
+                                                w.se2_long ? &w.lz.a : nullptr));
+        w.pl.se2_pre.launches.push_back(head_launch(ctx, B, TNs2, 0, w.pooled2.p, nullptr, ws.emb_fwd.p, nullptr, nullptr,
+                                                 nullptr, ws.step.get(), ws.scal.p, ws.iters_cap, PREC_F32));
     }
     // bf16, config.yaml shape: the head chains run inside the encoder kernels (se_head_fused
     // modes 0 / 1 / 3) instead of three se_head_v launches; AVC_FUSE_HEAD=0 keeps the launches
-    const char* fe = getenv("AVC_FUSE_HEAD");
     const bool head_ok = ctx->head_Wr16.p && c.c_h == FZ_C && c.c_out == FZ_C && c.n_dense_blocks == 6 &&
-                         !(fe && fe[0] == '0');
+                         !env_is("AVC_FUSE_HEAD", '0');
     const size_t head_lds = (size_t)(4 * c.n_dense_blocks + 8) * FZ_C * sizeof(float);
     for (int kind = 0; kind < 2; ++kind)
         for (int prec = 0; prec < 2; ++prec) {
-            Plan& pl = w.it[kind][prec];
+            Plan& pl = w.pl.it[kind][prec];
             const bool fh1 = prec == PREC_BF16 && head_ok && !ws.lz && (shS == 0 || shS == 16);    // SE(adv) fwd / bwd
             const bool fh2 = prec == PREC_BF16 && head_ok && !w.se2_long && (shS2 == 0 || shS2 == 16);   // fb: SE(dec)
             {   // SE(adv): masks + time-mean; advances the step counter
                 FusedArgs A = enc_args(c, nbS, B, ws.Tl, ctx->fzw[prec]);
                 A.x = ws.adv.p;
                 A.pooled = ws.pooled.p;
-                A.masks = ws.masks;
+                A.masks = ws.masks.get();
                 A.mask_words = ws.mask_words;
                 A.write_masks = 1;
-                A.tick = ws.step;
-                Launch F = enc_launch(L_FZ_FWD, prec, A, shS, c.kernel_size, se_fl, "se", ws.lz ? &ws.lza : nullptr);
+                A.tick = ws.step.get();
+                Launch F = enc_launch(L_FZ_FWD, prec, A, shS, c.kernel_size, se_fl, "se", ws.lz ? &ws.lzs.a : nullptr);
                 Launch H = head_launch(ctx, B, TNs, 0, ws.pooled.p, nullptr, w.emb.p, nullptr, nullptr, nullptr,
-                                       ws.step, ws.scal.p, ws.iters_cap, prec);
+                                       ws.step.get(), ws.scal.p, ws.iters_cap, prec);
                 if (fh1) {   // embedding + dense activations from the forward's tail
                     F.fz.fuse_head = 2;
                     F.fz.head = H.head;
@@ -869,7 +802,7 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
                 df.dz.org_out = w.org_out.p;
                 df.dz.g_out = w.gout.p;
                 df.dz.losses = ws.losses.p;
-                df.dz.step = ws.step;
+                df.dz.step = ws.step.get();
                 df.dz.scal = ws.scal.p;
                 df.dz.loss_len = ws.iters_cap;
                 if (!w.dec_long) df.dz.out = nullptr;   // nothing reads the output in an e2e iteration
@@ -880,13 +813,13 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
                 FusedArgs A = enc_args(c, nbS, B, w.Tl_se2, ctx->fzw[prec]);
                 A.x = w.out.p;
                 A.pooled = w.pooled2.p;
-                A.masks = w.masks2;
+                A.masks = w.masks2.get();
                 A.mask_words = ws.mask_words;
                 A.write_masks = 1;
                 Launch F2 = enc_launch(L_FZ_FWD, prec, A, shS2, c.kernel_size, se2_fl, "se2",
-                                       w.se2_long ? &w.lz : nullptr);
+                                       w.se2_long ? &w.lz.a : nullptr);
                 Launch H2 = head_launch(ctx, B, TNs2, 1, w.pooled2.p, w.gpooled2.p, w.emb.p, ws.tgt.p, ws.org.p,
-                                        ws.losses.p, ws.step, ws.scal.p, ws.iters_cap, prec);
+                                        ws.losses.p, ws.step.get(), ws.scal.p, ws.iters_cap, prec);
                 if (fh2) {   // the emb-loss chain in SE(dec)'s tail; the loss row is written by its bwd
                     F2.fz.fuse_head = 1;
                     F2.fz.head = H2.head;
@@ -901,7 +834,7 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
                 FusedArgs G = A;
                 G.write_masks = 0;
                 G.g_pooled = w.gpooled2.p;
-                G.step = ws.step;
+                G.step = ws.step.get();
                 G.scal = ws.scal.p;
                 G.table_len = ws.iters_cap;
                 G.gx_out = w.gdec.p;
@@ -911,7 +844,7 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
                     G.loss_len = ws.iters_cap;
                 }
                 pl.launches.push_back(enc_launch(L_FZ_BWD, prec, G, shS2, c.kernel_size, se2_fl, "se2",
-                                                 w.se2_long ? &w.lz : nullptr));
+                                                 w.se2_long ? &w.lz.a : nullptr));
                 db.dz.g_in = w.gdec.p;
             }
             pl.launches.push_back(db);
@@ -920,10 +853,10 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
             pl.launches.push_back(dense_launch(S->affT.p, w.gcond.p, nullptr, w.gemb.p, FZ_C, M, B, "dense_affine_T",
                                                4 * nd));
             Launch H3 = head_launch(ctx, B, TNs, 3, ws.pooled.p, ws.gpooled.p, w.emb.p, w.gemb.p, w.gemb.p, nullptr,
-                                    ws.step, ws.scal.p, ws.iters_cap, prec);
+                                    ws.step.get(), ws.scal.p, ws.iters_cap, prec);
             H3.head.tgt_parts = 4 * nd;
             if (!fh1) pl.launches.push_back(H3);
-            if (plan_fused_backward(ctx, ws, pl, prec)) return drop_vc_ws(ctx);
+            if (plan_fused_backward(ctx, ws, pl, prec)) return 1;
             if (fh1) {   // d loss / d emb -> g_pooled at the start of SE(adv)'s backward
                 Launch& Bk = pl.launches.back();
                 Bk.fz.fuse_head = 3;
@@ -934,47 +867,7 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
             }
         }
     w.ws_gen = ws.gen;
-    w.built = true;
     return 0;
-}
-
-// n_iters iterations of `iter` on the ctx stream: graph replay (captured once per plan),
-// plain launches, or per-kernel profiling
-static int run_iterations(avc_ctx* ctx, Plan& iter, hipGraphExec_t& graph, int n_iters, bool use_graph) {
-    if (ctx->profiling) {
-        hipEvent_t a, b;
-        HIPCHK(hipEventCreate(&a));
-        HIPCHK(hipEventCreate(&b));
-        HIPCHK(hipEventRecord(a, ctx->stream));
-        for (int it = 0; it < n_iters; ++it)
-            if (run_plan(ctx, iter, true)) return 1;
-        HIPCHK(hipEventRecord(b, ctx->stream));
-        HIPCHK(hipEventSynchronize(b));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, a, b));
-        ctx->prof_iter_ms += ms;
-        ctx->prof_iters += n_iters;
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-        return 0;
-    }
-    if (use_graph && n_iters > 0 && !(getenv("AVC_NO_GRAPH") && getenv("AVC_NO_GRAPH")[0] == '1'))
-        return graph_replay(ctx, iter, graph, n_iters);
-    for (int it = 0; it < n_iters; ++it)
-        if (run_plan(ctx, iter, false)) return 1;
-    return 0;
-}
-
-static int d2d(avc_ctx* ctx, void* dst, const void* src, size_t nfloat) {
-    HIPCHK(hipMemcpyAsync(dst, src, nfloat * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    return 0;
-}
-
-// emb of x [B][80][T] into ws.emb_fwd (fp32 forward plan)
-static int se_embed(avc_ctx* ctx, const float* x) {
-    Workspace& ws = *ctx->cur;
-    if (d2d(ctx, ws.xin.p, x, (size_t)ws.B * FZ_CIN * ws.T)) return 1;
-    return run_plan(ctx, ws.fwd, false);
 }
 
 // Decoder(ContentEncoder(src).mu, emb): emb [B][c_out] given (emb_dev) or SE(tgt) at Ts frames
@@ -986,13 +879,13 @@ static int inference_impl(avc_ctx* ctx, const float* src, int Ts, const float* t
     if (begin_call(ctx, us)) return 1;
     VcWs& w = *ctx->vc->cur;
     Workspace& ws = *ctx->cur;
-    if (d2d(ctx, w.src.p, src, (size_t)B * FZ_CIN * Ts) || run_plan(ctx, w.ce, false)) return 1;
+    if (d2d(ctx, w.src.p, src, (size_t)B * FZ_CIN * Ts) || run_plan(ctx, w.pl.ce, false)) return 1;
     if (tgt) {
         if (se_embed(ctx, tgt)) return 1;
     } else if (d2d(ctx, ws.emb_fwd.p, emb_dev, (size_t)B * ctx->cfg.c_out)) {
         return 1;
     }
-    if (run_plan(ctx, w.dec_pre, false)) return 1;
+    if (run_plan(ctx, w.pl.dec_pre, false)) return 1;
     if (d2d(ctx, out, w.out.p, (size_t)B * DZ_COUT * w.Tn)) return 1;
     return end_call(ctx, us);
 }
@@ -1016,14 +909,8 @@ static int vc_attack(avc_ctx* ctx, int kind, const float* vc_src, int Ts, const 
     const char* nm = kind == 0 ? "avc_e2e_attack" : "avc_fb_attack";
     if (!ctx || !vc_src || !vc_tgt || !(adv_tgt || tgt_emb) || !ptb0 || !out_adv) return fail("%s: null argument", nm);
     if (n_iters < 0) return fail("n_iters must be >= 0");
-    avc_attack_opts o{};
-    o.use_graph = 1;
-    if (opts) o = *opts;
-    if (o.precision != AVC_PREC_FP32 && o.precision != AVC_PREC_BF16) return fail("bad precision %d", o.precision);
-    if (o.reduction != AVC_REDUCE_INDEPENDENT && o.reduction != AVC_REDUCE_MEAN)
-        return fail("bad reduction %d", o.reduction);
-    if (o.update != AVC_UPDATE_ADAM && !(o.update == AVC_UPDATE_PGD && o.pgd_step > 0.f))
-        return fail("bad update %d (PGD needs pgd_step > 0)", o.update);
+    avc_attack_opts o;
+    if (attack_opts(opts, &o)) return 1;
     hipStream_t us = (hipStream_t)stream;
     if (ensure_vc_ws(ctx, B, T, Ts, n_iters)) return 1;
     Workspace& ws = *ctx->cur;
@@ -1035,35 +922,27 @@ static int vc_attack(avc_ctx* ctx, int kind, const float* vc_src, int Ts, const 
     const bool mean = o.reduction == AVC_REDUCE_MEAN;
     const float g_emb = (float)(2.0 / ((mean ? (double)B : 1.0) * c.c_out));
     const float g_out = (float)(2.0 / ((mean ? (double)B : 1.0) * DZ_COUT * w.Tn));
-
-    const float scal[4] = {eps, g_emb, g_out, o.update == AVC_UPDATE_PGD ? o.pgd_step : 0.f};
-    if (stage_call_consts(ctx, n_iters, scal)) return 1;
+    if (stage_attack_consts(ctx, n_iters, eps, g_emb, g_out, o)) return 1;
 
     if (d2d(ctx, ws.vc.p, vc_tgt, X) || d2d(ctx, w.src.p, vc_src, (size_t)B * c.c_in * Ts)) return 1;
-    if (run_plan(ctx, w.ce, false)) return 1;                                  // mu = CE(vc_src)
+    if (run_plan(ctx, w.pl.ce, false)) return 1;                                  // mu = CE(vc_src)
     const size_t O = (size_t)B * DZ_COUT * w.Tn, Eb = (size_t)B * c.c_out;
     if (kind == 0) {
         // org_out = inference(vc_src, vc_tgt), tgt_out = inference(vc_src, adv_tgt)  (attack_utils.py:35-37)
-        if (se_embed(ctx, vc_tgt) || run_plan(ctx, w.dec_pre, false) || d2d(ctx, w.org_out.p, w.out.p, O)) return 1;
+        if (se_embed(ctx, vc_tgt) || run_plan(ctx, w.pl.dec_pre, false) || d2d(ctx, w.org_out.p, w.out.p, O)) return 1;
         if (adv_tgt ? se_embed(ctx, adv_tgt) : d2d(ctx, ws.emb_fwd.p, tgt_emb, Eb)) return 1;
-        if (run_plan(ctx, w.dec_pre, false) || d2d(ctx, w.tgt_out.p, w.out.p, O)) return 1;
+        if (run_plan(ctx, w.pl.dec_pre, false) || d2d(ctx, w.tgt_out.p, w.out.p, O)) return 1;
     } else {
         // org_emb = SE(inference(vc_src, vc_tgt)), tgt_emb = SE(adv_tgt)  (attack_utils.py:117-119)
-        if (se_embed(ctx, vc_tgt) || run_plan(ctx, w.dec_pre, false) || run_plan(ctx, w.se2_pre, false) ||
+        if (se_embed(ctx, vc_tgt) || run_plan(ctx, w.pl.dec_pre, false) || run_plan(ctx, w.pl.se2_pre, false) ||
             d2d(ctx, ws.org.p, ws.emb_fwd.p, Eb))
             return 1;
         if (adv_tgt ? (se_embed(ctx, adv_tgt) || d2d(ctx, ws.tgt.p, ws.emb_fwd.p, Eb)) : d2d(ctx, ws.tgt.p, tgt_emb, Eb))
             return 1;
     }
-    hipLaunchKernelGGL(attack_init, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, ctx->stream, ws.vc.p, ptb0,
-                       ws.ptb.p, ws.m.p, ws.v.p, ws.adv.p, eps, X, o.update == AVC_UPDATE_PGD ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(ws.step, 0, sizeof(int), ctx->stream));
-    if (run_iterations(ctx, w.it[kind][prec], w.graph[kind][prec], n_iters, o.use_graph != 0)) return 1;
-    if (d2d(ctx, out_adv, ws.adv.p, X)) return 1;
-    if (o.losses && n_iters > 0 && d2d(ctx, o.losses, ws.losses.p, (size_t)n_iters * B)) return 1;
-    if (o.grad0 && n_iters > 0 && d2d(ctx, o.grad0, ws.grad0.p, X)) return 1;
-    return end_call(ctx, us);
+    if (attack_begin(ctx, ptb0, eps, o)) return 1;
+    if (run_iterations(ctx, w.pl.it[kind][prec], w.pl.graph[kind][prec], n_iters, o.use_graph != 0)) return 1;
+    return attack_end(ctx, n_iters, out_adv, o, us);
 }
 
 extern "C" int avc_e2e_attack(avc_ctx* ctx, const float* vc_src, const float* vc_tgt, const float* adv_tgt,
@@ -1104,8 +983,8 @@ extern "C" int avc_content_encoder(avc_ctx* ctx, const float* x, int B, int T, f
     VcWs& w = *ctx->vc->cur;
     const size_t O = (size_t)B * FZ_C * w.Tce;
     if (d2d(ctx, w.src.p, x, (size_t)B * FZ_CIN * T)) return 1;
-    if (mu && (run_plan(ctx, w.ce, false) || d2d(ctx, mu, w.mu.p, O))) return 1;
-    if (log_sigma && (run_plan(ctx, w.ce_std, false) || d2d(ctx, log_sigma, w.lsig.p, O))) return 1;
+    if (mu && (run_plan(ctx, w.pl.ce, false) || d2d(ctx, mu, w.mu.p, O))) return 1;
+    if (log_sigma && (run_plan(ctx, w.pl.ce_std, false) || d2d(ctx, log_sigma, w.lsig.p, O))) return 1;
     return end_call(ctx, us);
 }
 
@@ -1135,7 +1014,7 @@ extern "C" int avc_decoder(avc_ctx* ctx, const float* z, int B, int Tz, const fl
     Workspace& ws = *ctx->cur;
     if (d2d(ctx, w.mu.p, z, (size_t)B * FZ_C * Tz) || d2d(ctx, ws.emb_fwd.p, cond, (size_t)B * ctx->vc->cfg.dec_c_cond))
         return 1;
-    if (run_plan(ctx, w.dec_pre, false)) return 1;
+    if (run_plan(ctx, w.pl.dec_pre, false)) return 1;
     if (d2d(ctx, out, w.out.p, (size_t)B * DZ_COUT * w.Tn)) return 1;
     return end_call(ctx, us);
 }

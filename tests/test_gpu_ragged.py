@@ -3,9 +3,10 @@
 Real utterances arrive at their own lengths (/root/reference/attack.py:41-56, data_utils.py:65-118);
 each length has its own reflect padding, ceil-mode pooling and time-mean (models.py:10-30, 275-343),
 so per-length buckets of real data hold one or two utterances and leave the GPU idle.  The ragged
-batch runs every length in ONE launch per pass (the long engine, per-workgroup length and packed
-offsets).  What it must equal: every utterance, bit for bit, its own single-utterance attack on the long
-engine (same kernels, same per-utterance arithmetic) -- adv, the loss history and the iteration-0
+batch runs every length in ONE launch per pass (per-workgroup length and packed offsets; the long engine,
+or the fused runtime-length kernels when every length is in (64, 128]).  What a long-engine batch must
+equal: every utterance, bit for bit, its own single-utterance attack on the long engine (same kernels,
+same per-utterance arithmetic) -- adv, the loss history and the iteration-0
 gradient -- in both precisions; in fp32 that is also the fused engine's result for T <= 128 (the long
 and fused engines are bitwise equal there, test_gpu_long.py), i.e. attack_utils.emb_attack's."""
 import pytest
@@ -99,6 +100,74 @@ def test_ragged_fused_runtime_lengths(full, prec, monkeypatch):
     c2.ktime_start()
     c2.emb_attack_ragged(vc, te, p0, 0.1, 3, precision=prec)
     assert any(k.startswith("lz_se_bwd") for k in c2.ktime_stop())
+
+
+def _fresh_ctx(m):
+    return avc_native.Context(avc_native.se_config(m.speaker_encoder), avc_native.flat_weights(m.speaker_encoder),
+                              DEV.index or 0)
+
+
+def _ragged_timed(ctx, vc, te, p0, prec):
+    ctx.ktime_start()
+    res = ctx.emb_attack_ragged(vc, te, p0, 0.1, 3, precision=prec, want_losses=True, want_grad0=True)
+    return res, ctx.ktime_stop()
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_ragged_engine_is_part_of_the_key(full, prec):
+    """The same ragged batch (every length in (64, 128]) first under AUTO -- the fused runtime-length kernels --
+    then after set_engine('long') on the same context: the second call runs the long engine (not the cached
+    fused workspace) and every utterance equals its own long-engine attack bit for bit."""
+    m, _ = full
+    lens = [127, 100, 65]
+    ctx = _fresh_ctx(m)
+    vc, at, p0 = _utts(lens, 15)
+    te = torch.cat([ctx.se_forward(a[None]) for a in at])
+    _, kt = _ragged_timed(ctx, vc, te, p0, prec)
+    assert not any(k.startswith("lz_") for k in kt), kt
+    ctx.set_engine("long")
+    try:
+        (outs, L, g0), kt = _ragged_timed(ctx, vc, te, p0, prec)
+        assert any(k.startswith("lz_se_bwd") for k in kt), kt
+        for b, T in enumerate(lens):
+            ref, Lr, gr = ctx.emb_attack(vc[b][None], None, p0[b][None], 0.1, 3, precision=prec, want_losses=True,
+                                         want_grad0=True, tgt_emb=te[b:b + 1])
+            assert torch.equal(outs[b], ref[0]), (T, float((outs[b] - ref[0]).abs().max()))
+            assert torch.equal(L[:, b], Lr[:, 0]), T
+            assert torch.equal(g0[b], gr[0]), T
+    finally:
+        ctx.set_engine("auto")
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_ragged_fused_switch_is_part_of_the_key(full, prec, monkeypatch):
+    """AVC_RAGGED_FUSED=0 set after an AUTO call on the same context: the next call runs the long engine."""
+    m, _ = full
+    ctx = _fresh_ctx(m)
+    vc, at, p0 = _utts([127, 100, 65], 15)
+    te = torch.cat([ctx.se_forward(a[None]) for a in at])
+    _, kt = _ragged_timed(ctx, vc, te, p0, prec)
+    assert not any(k.startswith("lz_") for k in kt), kt
+    monkeypatch.setenv("AVC_RAGGED_FUSED", "0")
+    _, kt = _ragged_timed(ctx, vc, te, p0, prec)
+    assert any(k.startswith("lz_se_bwd") for k in kt), kt
+
+
+def test_attack_many_ragged_bf16_fused_chunk(full):
+    """A bf16 ragged chunk with every length in (64, 128): the fused runtime-length kernels with per-workgroup
+    lengths -- each result equals attack_utils.emb_attack's bf16 attack of that utterance under AUTO (the same
+    kernels; its persistent launch equals per-pass launches by test_gpu_persist.py).  T = 128 is left out: alone
+    it runs the standard-shape kernel."""
+    m, ctx = full
+    ctx.set_engine("auto")
+    lens = [127, 100, 97, 80]
+    vc, at, p0 = _utts(lens, 16)
+    out = batching.attack_many("emb", [m], vc, at, 0.1, 12, ptb0s=p0, precision="bf16", max_batch=4, ragged=True)
+    for i, T in enumerate(lens):
+        ref = attack_utils.emb_attack(m, vc[i][None], at[i][None], 0.1, 12, ptb0=p0[i][None],
+                                      precision="bf16").detach()[0]
+        assert out[i].shape == (80, T)
+        assert torch.equal(out[i], ref), (i, T, float((out[i] - ref).abs().max()))
 
 
 def test_attack_many_ragged(full):
