@@ -115,6 +115,16 @@ SIGNATURES = [
     ("avc_fb_attack_emb", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                          ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(AttackOpts), ctypes.c_void_p]),
+    ("avc_inference_ragged", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("avc_e2e_attack_ragged", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.POINTER(AttackOpts), ctypes.c_void_p]),
+    ("avc_fb_attack_ragged", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.POINTER(AttackOpts), ctypes.c_void_p]),
     ("avc_e2e_attack", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                       ctypes.c_void_p, ctypes.POINTER(AttackOpts), ctypes.c_void_p]),
@@ -555,6 +565,90 @@ class Context:
         with self._lock:
             self._sn_call(run)
         return out, losses, grad0
+
+    def _packed(self, name: str, ts):
+        """A list of [80, T_b] mels -> (their lengths, one packed fp32 device array of [80][T_b] blocks)."""
+        c_in = self.cfg["c_in"]
+        for b, t in enumerate(ts):
+            _require_gpu(t)
+            if t.dim() != 2 or t.shape[0] != c_in:
+                raise RuntimeError(f"{name}[{b}]: expected [{c_in}, T], got {tuple(t.shape)}")
+        dev = ts[0].device
+        return [int(t.shape[1]) for t in ts], torch.cat([t.reshape(-1).to(dev, torch.float32) for t in ts]).contiguous()
+
+    @staticmethod
+    def _split(x, lens, rows):
+        res, off = [], 0
+        for T in lens:
+            res.append(x[off:off + rows * T].view(rows, T))
+            off += rows * T
+        return res
+
+    def inference_ragged(self, srcs, emb):
+        """avc_inference_ragged: ONE batch of sources of different lengths (srcs[b] [80, S_b]; emb [B, c_out] =
+        SpeakerEncoder(tgt_b), each embedded at its own length) -- every component is one launch over all of them
+        on the long engine.  Returns the list of outputs [80, Tn(S_b)]."""
+        B = len(srcs)
+        if B == 0:
+            raise RuntimeError("inference_ragged: at least one utterance")
+        sl, src = self._packed("src", srcs)
+        emb = self._tgt_emb(emb, B)
+        tn = []
+        for S in sl:
+            n = lib().avc_vc_out_frames(self.h, S)
+            if n < 0:
+                raise RuntimeError(f"inference_ragged: source of {S} frames too short: " +
+                                   lib().avc_last_error().decode(errors="replace"))
+            tn.append(n)
+        out = torch.empty(80 * sum(tn), device=src.device, dtype=torch.float32)
+        arr = (ctypes.c_int * B)(*sl)
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+        with self._lock:
+            self._sn_call(lambda: _check(lib().avc_inference_ragged(
+                self.h, ctypes.c_void_p(src.data_ptr()), arr, B, ctypes.c_void_p(emb.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))))
+        return self._split(out, tn, 80)
+
+    def vc_attack_ragged(self, kind: str, vc_srcs, vc_tgts, tgt_emb, ptb0s, eps: float, n_iters: int, precision="fp32",
+                         reduction="independent", use_graph=True, want_losses=False, want_grad0=False, update="adam",
+                         pgd_step=1e-3):
+        """kind "e2e" (avc_e2e_attack_ragged) or "fb" (avc_fb_attack_ragged): ONE batch of utterances of different
+        lengths -- vc_srcs[b] [80, S_b], vc_tgts[b] and ptb0s[b] [80, T_b], tgt_emb [B, c_out] = SpeakerEncoder(adv_tgt_b)
+        embedded at its own length.  Every pass of the ContentEncoder, Decoder and SpeakerEncoder(s) is one launch over
+        the whole batch on the long engine; utterance b equals its own vc_attack(..., tgt_emb=) under
+        set_engine("long") bit for bit.  Returns (adv list [80, T_b], losses [n_iters, B] or None, grad0 list or
+        None).  Only independent per-utterance attacks (reduction "independent")."""
+        if kind not in ("e2e", "fb"):
+            raise RuntimeError(f"vc_attack_ragged: kind must be 'e2e' or 'fb', got {kind!r}")
+        B = len(vc_tgts)
+        if B == 0 or len(ptb0s) != B:
+            raise RuntimeError("vc_attack_ragged: one ptb0 per utterance, at least one utterance")
+        if len(vc_srcs) != B:
+            raise RuntimeError(f"vc_attack_ragged: {len(vc_srcs)} source lengths for B={B} utterances")
+        lens, vc = self._packed("vc_tgt", vc_tgts)
+        plens, p0 = self._packed("ptb0", ptb0s)
+        sl, src = self._packed("vc_src", vc_srcs)
+        if plens != lens:
+            raise RuntimeError("vc_attack_ragged: ptb0 lengths differ from vc_tgt lengths")
+        dev = vc.device
+        p0, src = p0.to(dev), src.to(dev)
+        tgt_emb = self._tgt_emb(tgt_emb, B)
+        out = torch.empty_like(vc)
+        o, losses, _ = self._opts(precision, reduction, use_graph, n_iters, torch.empty(B, 1, device=dev), want_losses,
+                                  False, update, pgd_step)
+        grad0 = torch.empty_like(vc) if want_grad0 and n_iters > 0 else None
+        if grad0 is not None:
+            o.grad0 = grad0.data_ptr()
+        la, sa = (ctypes.c_int * B)(*lens), (ctypes.c_int * B)(*sl)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        fn = {"e2e": lib().avc_e2e_attack_ragged, "fb": lib().avc_fb_attack_ragged}[kind]
+        with self._lock:
+            self._sn_call(lambda: _check(fn(
+                self.h, ctypes.c_void_p(src.data_ptr()), sa, ctypes.c_void_p(vc.data_ptr()), la, B,
+                ctypes.c_void_p(tgt_emb.data_ptr()), ctypes.c_void_p(p0.data_ptr()), float(eps), int(n_iters),
+                ctypes.c_void_p(out.data_ptr()), ctypes.byref(o), ctypes.c_void_p(stream))))
+        c_in = self.cfg["c_in"]
+        return self._split(out, lens, c_in), losses, (self._split(grad0, lens, c_in) if grad0 is not None else None)
 
     def ws_stats(self) -> Dict[str, int]:
         """avc_ws_stats: workspace builds / replans / hits, graph captures, evictions."""

@@ -1,7 +1,7 @@
 """Length-bucketed batching for real data (hard part 4).
 
 The reference attacks one utterance per call, at the length its wav gave it
-(/root/reference/attack.py:41-56 loads vc_tgt, adv_tgt and vc_src from three files).  Reflect
+(attack.py:41-56 loads vc_tgt, adv_tgt and vc_src from three files).  Reflect
 padding, ceil-mode pooling and InstanceNorm statistics all depend on that length
 (models.py:10-30, 206, 176), so utterances of different lengths cannot be zero-padded into one
 batch.  `attack_many` therefore
@@ -32,6 +32,13 @@ lengths below 128 (the same runtime-length kernels).  In fp32 the two engines ar
 (tests/test_gpu_long.py), so there every utterance equals attack_utils.emb_attack's result.  libavc
 caches one workspace (buffers, plans, captured graphs) per shape and engine, and attack_many sizes that
 cache to the shapes it uses, so a second call over the same lengths re-plans nothing (avc_ws_stats).
+
+`attack_many_ragged` is the ragged batch for all three attacks.  e2e / fb buckets are keyed by (T, T_src),
+two independent lengths of real data, so they are emptier still; a ragged e2e / fb chunk holds up to max_batch
+utterances of any (T, T_src) (avc_e2e_attack_ragged / avc_fb_attack_ragged), longest first by T + T_src, and runs
+every component -- ContentEncoder, Decoder, both SpeakerEncoder passes -- on the long engine, one launch per pass.
+Utterance i equals attack_utils.e2e_attack / fb_attack on it alone under the forced long engine
+(AVC_ENGINE_LONG) bit for bit.  Its emb kind is attack_many(ragged=True).
 """
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -68,6 +75,16 @@ def assign(costs: Sequence[float], n_dev: int) -> List[List[int]]:
     return [sorted(o) for o in own]
 
 
+def ragged_chunks(keys: Sequence[Tuple[int, int]], max_batch: int) -> List[List[int]]:
+    """Ragged chunks of utterances with keys (T, T_src): every index once, ordered longest first by the cost
+    T + T_src (ties in input order) and cut into chunks of at most max_batch -- neighbouring workgroups carry
+    similar work, and the chunks' costs do not increase."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be >= 1")
+    order = sorted(range(len(keys)), key=lambda i: (-(keys[i][0] + keys[i][1]), i))
+    return [order[s:s + max_batch] for s in range(0, len(order), max_batch)]
+
+
 def _mel(name: str, t: torch.Tensor) -> torch.Tensor:
     if t.dim() == 3 and t.shape[0] == 1:
         t = t[0]
@@ -76,15 +93,9 @@ def _mel(name: str, t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def attack_many(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts: Sequence[torch.Tensor],
-                adv_tgts: Sequence[torch.Tensor], eps: float, n_iters: int,
-                vc_srcs: Optional[Sequence[torch.Tensor]] = None, ptb0s: Optional[Sequence[torch.Tensor]] = None,
-                precision: str = "fp32", max_batch: int = 256, ragged: bool = False) -> List[torch.Tensor]:
-    """emb / e2e / fb attack (attack_utils.py:51-86 / 7-48 / 89-130) of a list of utterances of any
-    lengths: vc_tgts[i] [80, T_i], adv_tgts[i] [80, T'_i], vc_srcs[i] [80, S_i] (e2e / fb).
-    Returns [vc_tgts[i] + eps * tanh(ptb_i)] ([80, T_i] each, on the first model's device).
-    ptb0s[i] ([80, T_i]) as the reference's N(0,1) draw; drawn per utterance in input order on
-    the first model's device when omitted (attack_utils.py:68)."""
+def _prepare(kind, model_per_device, vc_tgts, adv_tgts, vc_srcs, ptb0s):
+    """The checks and normalisation every attack_many* shares: (devices, vc_tgts, adv_tgts, vc_srcs, ptb0s) with
+    one [80, T] mel per utterance; ptb0s drawn per utterance in input order when omitted."""
     if kind not in ("emb", "e2e", "fb"):
         raise ValueError(f"unknown attack {kind!r}")
     n = len(vc_tgts)
@@ -92,9 +103,9 @@ def attack_many(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts:
         raise ValueError("vc_tgts, adv_tgts, vc_srcs and ptb0s must have one entry per utterance")
     if kind != "emb" and vc_srcs is None:
         raise ValueError("e2e / fb attacks need vc_srcs")
-    if n == 0:
-        return []
     devs = [next(m.parameters()).device for m in model_per_device]
+    if n == 0:
+        return devs, [], [], vc_srcs, []
     for m in model_per_device:
         check_no_train_dropout(m.speaker_encoder)
     vc_tgts = [_mel("vc_tgt", t) for t in vc_tgts]
@@ -106,9 +117,26 @@ def attack_many(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts:
     for i in range(n):
         if ptb0s[i].shape != vc_tgts[i].shape:
             raise ValueError(f"utterance {i}: ptb0 {tuple(ptb0s[i].shape)} != vc_tgt {tuple(vc_tgts[i].shape)}")
+    return devs, vc_tgts, adv_tgts, vc_srcs, ptb0s
+
+
+def attack_many(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts: Sequence[torch.Tensor],
+                adv_tgts: Sequence[torch.Tensor], eps: float, n_iters: int,
+                vc_srcs: Optional[Sequence[torch.Tensor]] = None, ptb0s: Optional[Sequence[torch.Tensor]] = None,
+                precision: str = "fp32", max_batch: int = 256, ragged: bool = False) -> List[torch.Tensor]:
+    """emb / e2e / fb attack (attack_utils.py:51-86 / 7-48 / 89-130) of a list of utterances of any
+    lengths: vc_tgts[i] [80, T_i], adv_tgts[i] [80, T'_i], vc_srcs[i] [80, S_i] (e2e / fb).
+    Returns [vc_tgts[i] + eps * tanh(ptb_i)] ([80, T_i] each, on the first model's device).
+    ptb0s[i] ([80, T_i]) as the reference's N(0,1) draw; drawn per utterance in input order on
+    the first model's device when omitted (attack_utils.py:68)."""
+    n = len(vc_tgts)
+    devs, vc_tgts, adv_tgts, vc_srcs, ptb0s = _prepare(kind, model_per_device, vc_tgts, adv_tgts, vc_srcs, ptb0s)
+    if n == 0:
+        return []
 
     if ragged and kind != "emb":
-        raise ValueError("ragged batches are built for the emb attack only")
+        raise ValueError("ragged batches are built for the emb attack only here: attack_many_ragged runs ragged "
+                         "e2e / fb batches")
     # the attack chunks: equal (T, S) within a chunk -- or, ragged, any lengths, longest first
     keys = [(vc_tgts[i].shape[1], vc_srcs[i].shape[1] if vc_srcs is not None else 0) for i in range(n)]
     if ragged:
@@ -167,6 +195,68 @@ def attack_many(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts:
                                                   tgt_emb=te)
                     for k, i in enumerate(ids):
                         results[i] = out[k]
+                torch.cuda.current_stream(dev).synchronize()
+        except BaseException as e:  # re-raised on the calling thread
+            errs.append(e)
+
+    threads = [threading.Thread(target=work, args=(d,)) for d in range(len(devs))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errs:
+        raise errs[0]
+    return [r.to(devs[0]) for r in results]
+
+
+def attack_many_ragged(kind: str, model_per_device: Sequence[torch.nn.Module], vc_tgts: Sequence[torch.Tensor],
+                       adv_tgts: Sequence[torch.Tensor], eps: float, n_iters: int,
+                       vc_srcs: Optional[Sequence[torch.Tensor]] = None, ptb0s: Optional[Sequence[torch.Tensor]] = None,
+                       precision: str = "fp32", max_batch: int = 256) -> List[torch.Tensor]:
+    """attack_many with ragged batches for every kind: chunks of up to max_batch utterances of ANY lengths
+    (ragged_chunks: longest first by T + T_src), dealt to the devices by that cost, each chunk ONE ragged call
+    (Context.emb_attack_ragged / vc_attack_ragged).  Arguments and result as attack_many's."""
+    n = len(vc_tgts)
+    devs, vc_tgts, adv_tgts, vc_srcs, ptb0s = _prepare(kind, model_per_device, vc_tgts, adv_tgts, vc_srcs, ptb0s)
+    if n == 0:
+        return []
+    keys = [(vc_tgts[i].shape[1], vc_srcs[i].shape[1] if kind != "emb" else 0) for i in range(n)]
+    chunks = ragged_chunks(keys, max_batch)
+    owner = assign([sum(sum(keys[i]) for i in c) * max(n_iters, 1) for c in chunks], len(devs))
+    need = [sorted({i for j in owner[d] for i in chunks[j]}) for d in range(len(devs))]
+    results: List[Optional[torch.Tensor]] = [None] * n
+    errs: List[BaseException] = []
+
+    def work(d: int):
+        try:
+            if not owner[d]:
+                return
+            dev = devs[d]
+            m = model_per_device[d]
+            with torch.cuda.device(dev):
+                ctx = context_for(m.speaker_encoder, dev) if kind == "emb" else vc_context_for(m, dev)
+                adv_groups = buckets([adv_tgts[i].shape[1] for i in need[d]], max_batch)
+                # one SpeakerEncoder workspace per adv_tgt group and per chunk (+ a VC one per chunk, in its own
+                # cache of the same cap): a repeated call over the same lengths re-plans nothing
+                ctx.set_ws_cache(min(64, max(6, len(adv_groups) + len(owner[d]) + 2)))
+                emb: Dict[int, torch.Tensor] = {}
+                for g in adv_groups:
+                    ids = [need[d][k] for k in g]
+                    e = ctx.se_forward(torch.stack([adv_tgts[i] for i in ids]).to(dev, torch.float32).contiguous())
+                    for k, i in enumerate(ids):
+                        emb[i] = e[k]
+                for j in owner[d]:
+                    ids = chunks[j]
+                    te = torch.stack([emb[i] for i in ids]).contiguous()
+                    vc = [vc_tgts[i].to(dev, torch.float32) for i in ids]
+                    p0 = [ptb0s[i].to(dev, torch.float32) for i in ids]
+                    if kind == "emb":
+                        outs, _, _ = ctx.emb_attack_ragged(vc, te, p0, eps, n_iters, precision=precision)
+                    else:
+                        outs, _, _ = ctx.vc_attack_ragged(kind, [vc_srcs[i].to(dev, torch.float32) for i in ids], vc, te,
+                                                          p0, eps, n_iters, precision=precision)
+                    for k, i in enumerate(ids):
+                        results[i] = outs[k]
                 torch.cuda.current_stream(dev).synchronize()
         except BaseException as e:  # re-raised on the calling thread
             errs.append(e)

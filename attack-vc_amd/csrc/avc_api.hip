@@ -1423,8 +1423,9 @@ static int enc_block_lengths(avc_ctx* ctx, int T, std::vector<int>& Tl) {
 // The cache key of a call: B utterances of T frames, or (lens non-null) a ragged batch of B utterances of
 // lens[b] frames.  A ragged batch runs the fused runtime-length kernels with a per-workgroup length when
 // every length is in (64, 128] of the standard config (T = 128 is then the workspace's bound: LDS layout,
-// mask words), otherwise the long engine at T = the longest; never the layered engine.
-static int resolve_key(avc_ctx* ctx, int B, int T, const std::vector<int>* lens, SeKey& k) {
+// mask words), otherwise the long engine at T = the longest; never the layered engine.  rag_long: the long
+// engine whatever the lengths (the ragged e2e / fb attacks run every component on it).
+static int resolve_key(avc_ctx* ctx, int B, int T, const std::vector<int>* lens, SeKey& k, bool rag_long = false) {
     if (B <= 0) return fail("batch size must be positive (got %d)", B);
     k.B = B;
     if (!lens) {
@@ -1437,7 +1438,7 @@ static int resolve_key(avc_ctx* ctx, int B, int T, const std::vector<int>* lens,
         return fail("ragged batches run on the long engine (fused-capable config, engine not layered)");
     const int Tmin = *std::min_element(lens->begin(), lens->end());
     const int Tmax = *std::max_element(lens->begin(), lens->end());
-    const bool rag_fused = Tmin > 64 && Tmax <= 128 && ctx->engine != AVC_ENGINE_LONG && !env_is("AVC_RAGGED_FUSED", '0') &&
+    const bool rag_fused = !rag_long && Tmin > 64 && Tmax <= 128 && ctx->engine != AVC_ENGINE_LONG && !env_is("AVC_RAGGED_FUSED", '0') &&
                            fused_shape(ctx, 100) == 16 && !env_is("AVC_LONG", '1');
     k.T = rag_fused ? 128 : Tmax;
     k.engine = rag_fused ? AVC_ENGINE_FUSED : AVC_ENGINE_LONG;
@@ -1536,9 +1537,10 @@ static int plan_ws(avc_ctx* ctx, Workspace& ws, int cap) {
 
 // The workspace of a call (ctx->cur) with tables for n_iters iterations: resolve the key, look it
 // up, build a new entry or re-plan one whose tables are too short, plan.
-static int ensure_ws(avc_ctx* ctx, int B, int T, int n_iters, const std::vector<int>* lens = nullptr) {
+static int ensure_ws(avc_ctx* ctx, int B, int T, int n_iters, const std::vector<int>* lens = nullptr,
+                     bool rag_long = false) {
     SeKey k;
-    if (resolve_key(ctx, B, T, lens, k)) return 1;
+    if (resolve_key(ctx, B, T, lens, k, rag_long)) return 1;
     ctx->cur = ctx->wss.find(k);
     if (ctx->cur && n_iters <= ctx->cur->iters_cap) {
         ++ctx->n_ws_hits;

@@ -150,10 +150,13 @@ struct FusedW {
 // length.  Its input / Adam state start at float offset xoff of the packed arrays ([80][T_b] blocks, one
 // after the other); the scratch slots (LongArgs) are sized for the longest.
 // (The block lengths follow from T: Tl[l+1] = ceil(Tl[l] / sub[l]), avc_long.hip lz_tl.)
+// The ragged e2e / fb attacks use the same table for the ContentEncoder (T = source frames, moff = where its
+// [128][T_N] block of mu_out starts) and for the SpeakerEncoder over the packed decoder output.
 struct RagUtt {
     int32_t T;
     int32_t pad_;
     int64_t xoff;
+    int64_t moff;                     // ce_mode: float offset of this utterance's mu_out block
 };
 
 struct FusedArgs {
@@ -246,6 +249,18 @@ struct DecW {
     const float* b_out;
 };
 
+// Ragged batch (long Decoder, avc_*_attack_ragged / avc_inference_ragged): utterance b has T0 content frames
+// and Tn = T0 * prod(up) output frames; its mu / output-sized / stash blocks start at these float offsets of
+// the packed arrays (blocks one after the other, nothing behind the last).  The layer lengths and the stash
+// offsets inside the block follow from T0 (avc_long.hip lz_dec_tl / lz_dec_so).
+struct DecUtt {
+    int32_t T0;
+    float gscale;                     // 2 / (80 Tn): this utterance's scal[2] (e2e loss-gradient scale)
+    int64_t mu_off;                   // [128][T0] block of mu
+    int64_t out_off;                  // [80][Tn] block of out, g_out, g_in, tgt_out, org_out
+    int64_t stash_off;                // stash block
+};
+
 struct DecArgs {
     int32_t B, ks, nblk, act;
     int32_t up[DZ_MAXBLK];
@@ -268,6 +283,8 @@ struct DecArgs {
     // bwd
     const float* g_in;                // [B][80][Tl[nblk]] d loss / d out
     float* g_cond;                    // [B][2*nblk][256]
+    const DecUtt* rag;                // long engine: per-workgroup lengths / offsets (null: every utterance
+                                      // Tl[0] content frames, blocks at b * their size)
     DecW w;
 };
 

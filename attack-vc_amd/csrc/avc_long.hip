@@ -842,7 +842,7 @@ __device__ __forceinline__ void lz_se_fwd_body(FusedArgs A, LongArgs L) {
         f32x4 bm[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) bm[i] = *reinterpret_cast<const f32x4*>(A.w.b_mean + ch0 + 16 * i);
-        float* mu = A.mu_out + (size_t)b * FZ_C * TN;
+        float* mu = A.mu_out + (ru ? (size_t)ru->moff : (size_t)b * FZ_C * TN);
         LzChunk chk;
         const int nfn = lz_nf(TN);
         for (int k = 0; lz_chunk(k, nfn, NF, chk); ++k) {
@@ -1383,6 +1383,24 @@ __device__ __forceinline__ void lz_ct_to_img(char* img, const float* src, int T)
     }
 }
 
+// Input length of Decoder block l (l = nblk: the output) for T0 content frames, and the float offset of
+// InstanceNorm layer q's stash inside an utterance's block (layer q spans the frames of block (q + 1) / 2's
+// input, 2048 floats per 16-frame fragment: the host's build_vc_ws layout).  From the workgroup's own T0 by
+// arithmetic, as lz_tl (a ragged batch has one T0 per utterance).
+__device__ __forceinline__ int lz_dec_tl(const DecArgs& A, int T0, int l) {
+    int t = T0;
+    for (int k = 0; k < l; ++k) t *= A.up[k];
+    return t;
+}
+__device__ __forceinline__ int lz_dec_so(const DecArgs& A, int T0, int q) {
+    int t = T0, off = 0;
+    for (int p = 0; p < q; ++p) {
+        if (p & 1) t *= A.up[p >> 1];
+        off += 2048 * lz_nf(t);
+    }
+    return off;
+}
+
 template <int PREC>
 __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
     using Z = Lz<PREC>;
@@ -1390,15 +1408,16 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
     constexpr int VE = 16 / ESZ, KS = 4 * VE;
     constexpr int NF = LZ_CHF;
     const int b = blockIdx.x;
+    const DecUtt* const ru = A.rag ? A.rag + b : nullptr;   // ragged batch: this utterance's own length
     const int nblk = A.nblk, ks = A.ks, P = ks / 2, act = A.act;
-    const int T0 = A.Tl[0], Tn = A.Tl[nblk];
+    const int T0 = ru ? ru->T0 : A.Tl[0], Tn = lz_dec_tl(A, T0, nblk);
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, kq = lane >> 4;
     const int ch0 = 32 * w + 4 * kq;
     const float* cond = A.cond + (size_t)b * (2 * nblk) * 256;
     const bool stash = A.stash_per_utt > 0;
-    float* stb = A.stash + (size_t)b * A.stash_per_utt;
+    float* stb = A.stash + (ru ? (size_t)ru->stash_off : (size_t)b * A.stash_per_utt);
 
     char* imgh = L.img[0] + (size_t)b * L.img_stride;
     char* imgy = L.img[1] + (size_t)b * L.img_stride;
@@ -1419,7 +1438,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
     LzMom mom;
     mom.n = 0.f;
 
-    lz_ct_to_img<PREC, FZ_C>(imgy, A.mu + (size_t)b * FZ_C * T0, T0);   // mu -> in_conv operand
+    lz_ct_to_img<PREC, FZ_C>(imgy, A.mu + (ru ? (size_t)ru->mu_off : (size_t)b * FZ_C * T0), T0);   // mu -> in_conv operand
     lz_publish();
     // in_conv (1x1) + b -> raw
     {
@@ -1495,7 +1514,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
 
     int cur = 0;
     for (int l = 0; l < nblk; ++l) {
-        const int Ti = A.Tl[l], up = A.up[l], To = Ti * up;
+        const int Ti = lz_dec_tl(A, T0, l), up = A.up[l], To = Ti * up;
         f32x4 b1[2], b2[2][2], mn1[2], sd1[2], mn2[2], sd2[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1540,7 +1559,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
                     for (int i = 0; i < 2; ++i) *lz_fl(raw, n0 + 16 * f + c, w, i) = acc[i][f];
             lz_mom_add(mom, acc, own);
         }
-        float* st1 = stb + A.stash_off[2 * l];
+        float* st1 = stb + lz_dec_so(A, T0, 2 * l);
         in_pass(Ti, no_ld, [&](int t, int i, f32x4 yh, f32x4 inv, f32x4) __attribute__((always_inline)) {
             if (stash) lz_stash_put<PREC>(st1, t, w, i, yh);
             if (t == c) put_inv(2 * l, inv, i);
@@ -1581,7 +1600,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
                 lz_mom_add(mom, acc, own);
             }
         }
-        float* st2 = stb + A.stash_off[2 * l + 1];
+        float* st2 = stb + lz_dec_so(A, T0, 2 * l + 1);
         float* hin = hf[cur];
         float* hout = hf[cur ^ 1];
         // IN over the To frames -> AdaIN(2l+1) -> act -> + (nearest-upsampled) residual
@@ -1602,7 +1621,8 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
     // out_conv (1x1, 128 -> 80) + b -> out [80][Tn]; e2e: MSE(out, tgt) - 0.1 MSE(out, org)
     // (attack_utils.py:41-43), its gradient and the per-utterance loss
     const bool e2e = A.tgt_out != nullptr;
-    const float gscale = e2e ? A.scal[2] : 0.f;
+    const float gscale = e2e ? (ru ? ru->gscale : A.scal[2]) : 0.f;
+    const size_t ob = ru ? (size_t)ru->out_off : (size_t)b * DZ_COUT * Tn;   // this utterance's [80][Tn] blocks
     float q1 = 0.f, q2 = 0.f;
     float* OS = reinterpret_cast<float*>(fz_lds + 80 * 1024);   // [80][128] fp32 chunk of out
     const int tile0 = w < 2 ? 2 * w : 3;
@@ -1631,7 +1651,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
             }
         }
         __syncthreads();
-        float* outb = A.out + (size_t)b * DZ_COUT * Tn;
+        float* outb = A.out + ob;
         // UO elements per thread at a time: the targets' loads, one drain, then the stores (the
         // same per-thread order of the loss sums)
         constexpr int UO = 10;
@@ -1642,7 +1662,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
                 for (int u = 0; u < UO; ++u) {
                     const int idx = min(i0 + 256 * u, DZ_COUT * 128 - 1);
                     const int co = idx >> 7, t = min(n0 + (idx & 127), Tn - 1);
-                    const size_t qb = (size_t)b * DZ_COUT * Tn + (size_t)co * Tn + t;
+                    const size_t qb = ob + (size_t)co * Tn + t;
                     tg[u] = A.tgt_out[qb];
                     og[u] = A.org_out[qb];
                 }
@@ -1659,7 +1679,7 @@ __device__ __forceinline__ void lz_dec_fwd_body(DecArgs A, LongArgs L) {
                 const size_t q = (size_t)co * Tn + t;
                 outb[q] = o;
                 if (e2e) {
-                    const size_t qb = (size_t)b * DZ_COUT * Tn + q;
+                    const size_t qb = ob + q;
                     const float d1 = o - tg[u], d2 = o - og[u];
                     A.g_out[qb] = gscale * d1 + gscale * d2 * -0.1f;
                     q1 += d1 * d1;
@@ -1705,15 +1725,16 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
     constexpr int VE = 16 / ESZ, KS = 4 * VE;
     constexpr int NF = LZ_CHF;
     const int b = blockIdx.x;
+    const DecUtt* const ru = A.rag ? A.rag + b : nullptr;   // ragged batch: this utterance's own length
     const int nblk = A.nblk, ks = A.ks, P = ks / 2, act = A.act;
-    const int Tn = A.Tl[nblk];
+    const int T0 = ru ? ru->T0 : A.Tl[0], Tn = lz_dec_tl(A, T0, nblk);
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, kq = lane >> 4;
     const int ch0 = 32 * w + 4 * kq;
     const float* cond = A.cond + (size_t)b * (2 * nblk) * 256;
     float* gcond = A.g_cond + (size_t)b * (2 * nblk) * 256;
-    const float* stb = A.stash + (size_t)b * A.stash_per_utt;
+    const float* stb = A.stash + (ru ? (size_t)ru->stash_off : (size_t)b * A.stash_per_utt);
 
     char* imgg = L.img[1] + (size_t)b * L.img_stride;    // dY image (half 0), the out_conv^T operand
     char* imgg2 = L.img[2] + (size_t)b * L.img_stride;   // dY image of half 1
@@ -1734,7 +1755,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
     // g_in [80][Tn] -> image (channels 80..127 of each row zero: the K padding of out_conv^T)
     lz_zero_rows<PREC>(imgg, 0, LZ_ZR + Tn + 2 * LZ_ZR);
     lz_publish();
-    lz_ct_to_img<PREC, DZ_COUT>(imgg, A.g_in + (size_t)b * DZ_COUT * Tn, Tn);
+    lz_ct_to_img<PREC, DZ_COUT>(imgg, A.g_in + (ru ? (size_t)ru->out_off : (size_t)b * DZ_COUT * Tn), Tn);
     lz_publish();
     // g(h_N) = out_conv^T g_out -> gh[0]
     {
@@ -1766,7 +1787,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
     // (t, i, d/dx) to out.
     // pass 2 (and the d/d cond[q] store) from the pass-1 sums gm / gs
     auto adain_in_bwd_tail = [&](int q, int Tl, f32x4 (&gm)[2], f32x4 (&gs)[2], auto&& out) __attribute__((always_inline)) {
-        const float* yq = stb + A.stash_off[q];
+        const float* yq = stb + lz_dec_so(A, T0, q);
         f32x4 sd[2], is[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1819,7 +1840,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
         }
     };
     auto adain_in_bwd = [&](int q, int Tl, auto&& gsrc, auto&& out) __attribute__((always_inline)) {
-        const float* yq = stb + A.stash_off[q];
+        const float* yq = stb + lz_dec_so(A, T0, q);
         f32x4 mn[2], sd[2], gm[2], gs[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1865,7 +1886,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
     // that produces its input gradient (every block but the last, which starts from out_conv^T)
     f32x4 gm2[2], gs2[2];
     for (int l = nblk - 1; l >= 0; --l) {
-        const int Ti = A.Tl[l], up = A.up[l], To = Ti * up;
+        const int Ti = lz_dec_tl(A, T0, l), up = A.up[l], To = Ti * up;
         float* gin = gh[cur];            // g(h_{l+1}) over To frames
         float* gout = gh[cur ^ 1];       // g(h_l) over Ti frames
         // conv2 branch: act, AdaIN(2l+1), IN backward over To frames -> dY image(s): frame
@@ -1892,7 +1913,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
         // owned frames: g_z -> tmp and its two row sums (the sums in the order a separate pass over
         // the frames would take: bitwise the same, one fp32 stream write + read fewer)
         const int nfc = lz_nf(Ti + 16 + P);
-        const float* yq1 = stb + A.stash_off[2 * l];
+        const float* yq1 = stb + lz_dec_so(A, T0, 2 * l);
         f32x4 mn1[2], sd1[2], gm1[2], gs1[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1960,7 +1981,7 @@ __device__ __forceinline__ void lz_dec_bwd_body(DecArgs A, LongArgs L) {
         // conv1^T (+ fold) + the residual branch (adjoint of the x2 nearest upsample) -> g(h_l),
         // and on it the first pass of block l-1's conv2-branch IN backward (AdaIN(2l-1) over the
         // same Ti frames): g_z -> tmp, its row sums -> gm2 / gs2
-        const float* yq2 = stb + A.stash_off[2 * l - 1];
+        const float* yq2 = stb + lz_dec_so(A, T0, 2 * l - 1);
         f32x4 mn2[2], sd2[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {

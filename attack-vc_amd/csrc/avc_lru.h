@@ -78,14 +78,21 @@ struct SeKey {
 };
 
 // ContentEncoder / Decoder workspace of the e2e / fb attacks: attacked length T, source length Ts,
-// and whether the ContentEncoder / the Decoder run on the long engine.
+// and whether the ContentEncoder / the Decoder run on the long engine.  A ragged batch also carries its
+// attacked and source lengths (T / Ts are then the longest, both engines the long one); both vectors are
+// empty otherwise, so a ragged key never equals a uniform one.
 struct VcKey {
     int B = 0, T = 0, Ts = 0;
     bool ce_long = false, dec_long = false;
+    std::vector<int> lens, src_lens;
     bool operator==(const VcKey& o) const {
-        return B == o.B && T == o.T && Ts == o.Ts && ce_long == o.ce_long && dec_long == o.dec_long;
+        return B == o.B && T == o.T && Ts == o.Ts && ce_long == o.ce_long && dec_long == o.dec_long && lens == o.lens &&
+               src_lens == o.src_lens;
     }
-    void print(FILE* f) const { fprintf(f, "B=%d T=%d Ts=%d ce_long=%d dec_long=%d", B, T, Ts, (int)ce_long, (int)dec_long); }
+    void print(FILE* f) const {
+        fprintf(f, "B=%d T=%d Ts=%d ce_long=%d dec_long=%d ragged=%d", B, T, Ts, (int)ce_long, (int)dec_long,
+                (int)!src_lens.empty());
+    }
 };
 
 }  // namespace avc

@@ -22,6 +22,14 @@ struct VcWs {
     LongScratch lz;                       // their scratch (max(Ts, Tn) frames) + SE2's ballot masks
     int stash_per_utt = 0;
     std::vector<int> stash_off;
+    size_t S = 0, O = 0;                  // floats of the source array (B x 80 x Ts) and of an output-sized one
+                                          // (B x 80 x Tn), or their packed sums
+    // ragged batch (avc_*_attack_ragged / avc_inference_ragged): utterance b has its own source length, every
+    // array is packed blocks, every component runs on the long engine (scratch sized for the longest)
+    bool ragged = false;
+    DevPtr<RagUtt> rag_ce, rag_se2;       // ContentEncoder (Ts_b, source / mu offsets), SE over the decoder output (Tn_b)
+    DevPtr<DecUtt> rag_dec;
+    double fl_ce = 0, fl_se2 = 0, fl_dec[2] = {0, 0};   // algorithmic FLOPs over the batch (dec: fwd, bwd)
     int ws_gen = -1;                      // SpeakerEncoder workspace generation the plans point into
     struct Plans {                        // rebuilt whenever the SpeakerEncoder workspace is re-planned (renew)
         Plan ce, ce_std, dec_pre, se2_pre;
@@ -47,7 +55,7 @@ struct VcState {
     std::vector<SnChunk> sn_chunks[2];
     DevBuf sn_raw, sn_uv, sn_sigma, sn_layer_dev, sn_chunk_dev[2], sn_train;   // sn_train: 1 int (SnArgs.train)
     size_t sn_uv_count = 0;
-    // workspaces by VcKey {B, T, Ts, ce_long, dec_long}, most recently used first; each one's plans
+    // workspaces by VcKey {B, T, Ts, ce_long, dec_long, lens, src_lens}, most recently used first; each one's plans
     // point into the SpeakerEncoder workspace whose gen they record (ws_gen)
     LruCache<VcKey, VcWs> wss;
     VcWs* cur = nullptr;
@@ -618,8 +626,9 @@ static Launch dec_launch(avc_ctx* ctx, int kind, int prec, int B, const std::vec
     A.stash = w.stash.p;
     A.invstd = w.invstd.p;
     A.g_cond = w.gcond.p;
+    A.rag = w.rag_dec.get();
     A.w = S->dw[prec];
-    L.flop = 2.0 * dec_mac(v, Tl, kind == L_DZ_BWD) * B;
+    L.flop = w.ragged ? w.fl_dec[kind == L_DZ_BWD] : 2.0 * dec_mac(v, Tl, kind == L_DZ_BWD) * B;
     L.name = std::string(kind == L_DZ_FWD ? "dec_fwd_fused" : "dec_bwd_fused") + (prec == PREC_F32 ? "<f32>" : "<bf16>");
     if (w.dec_long) L.name = std::string(kind == L_DZ_FWD ? "lz_dec_fwd" : "lz_dec_bwd") + (prec == PREC_F32 ? "<f32>" : "<bf16>");
     return L;
@@ -645,6 +654,8 @@ static int build_vc_ws(avc_ctx* ctx, VcWs& w, const VcKey& k, const Workspace& w
     w.B = k.B;
     w.T = k.T;
     w.Ts = k.Ts;
+    w.S = (size_t)k.B * FZ_CIN * k.Ts;
+    w.O = (size_t)k.B * DZ_COUT * w.Tn;
     const int nd = v.dec_n_conv_blocks;
     // long engine for lengths past the fused engine's 128 frames (or when forced: then all three)
     w.ce_long = k.ce_long;
@@ -679,7 +690,84 @@ static int build_vc_ws(avc_ctx* ctx, VcWs& w, const VcKey& k, const Workspace& w
            alloc_long(w.lz, k.B, std::max(k.Ts, w.Tn), (int)ctx->bank_k.size() + 1 + 2 * c.n_conv_blocks);
 }
 
+// A source utterance's lengths through the ContentEncoder, the Decoder and the SpeakerEncoder over the
+// decoder output; `b` names the utterance in the message of one that is too short
+static int ragged_src_lengths(avc_ctx* ctx, int b, int Ts, std::vector<int>& tce, std::vector<int>& tdec,
+                              std::vector<int>& tse2) {
+    VcState* S = ctx->vc;
+    if (Ts <= 0 || enc_lengths(S->ce, S->ce_bank_k, Ts, tce) || dec_lengths(S->cfg, tce.back(), tdec) ||
+        enc_lengths(ctx->cfg, ctx->bank_k, tdec.back(), tse2))
+        return fail("ragged batch: source utterance %d has %d frames, too short for the reflect padding of the "
+                    "ContentEncoder / Decoder / SpeakerEncoder", b, Ts);
+    return 0;
+}
+
+// the lengths, tables and buffers of a new ragged VC workspace for key `k` (k.lens / k.src_lens) over the ragged
+// SpeakerEncoder workspace `ws`: buffers sized by sums of lengths, scratch for the longest utterance
+static int build_vc_ws_ragged(avc_ctx* ctx, VcWs& w, const VcKey& k, const Workspace& ws) {
+    VcState* S = ctx->vc;
+    const avc_se_cfg& c = ctx->cfg;
+    const avc_vc_cfg& v = S->cfg;
+    const int B = k.B, nd = v.dec_n_conv_blocks;
+    w.B = B;
+    w.T = k.T;
+    w.Ts = k.Ts;
+    w.ragged = w.ce_long = w.dec_long = w.se2_long = true;
+    // the plans' uniform fields (ignored by the kernels next to a table) describe the longest utterance
+    const int longest = (int)(std::max_element(k.src_lens.begin(), k.src_lens.end()) - k.src_lens.begin());
+    if (ragged_src_lengths(ctx, longest, k.Ts, w.Tl_ce, w.Tl_dec, w.Tl_se2)) return 1;
+    w.Tce = w.Tl_ce.back();
+    w.Tn = w.Tl_dec.back();
+    w.stash_off.assign(2 * DZ_MAXBLK, 0);   // (the long Decoder derives a layer's offset from the utterance's T0)
+    std::vector<RagUtt> rce(B), rse2(B);
+    std::vector<DecUtt> rdec(B);
+    std::vector<int> tce, tdec, tse2;
+    size_t mu = 0, stash = 0;
+    for (int b = 0; b < B; ++b) {
+        if (ragged_src_lengths(ctx, b, k.src_lens[b], tce, tdec, tse2)) return 1;
+        const int Tn = tdec.back();
+        rce[b] = RagUtt{k.src_lens[b], 0, (int64_t)w.S, (int64_t)mu};
+        rse2[b] = RagUtt{Tn, 0, (int64_t)w.O, 0};
+        // the gradient scale of the output MSE over this utterance's 80 x Tn elements: the arithmetic of a
+        // single-utterance call (vc_attack's g_out)
+        rdec[b] = DecUtt{tce.back(), (float)(2.0 / (1.0 * DZ_COUT * Tn)), (int64_t)mu, (int64_t)w.O, (int64_t)stash};
+        w.S += (size_t)FZ_CIN * k.src_lens[b];
+        w.O += (size_t)DZ_COUT * Tn;
+        mu += (size_t)FZ_C * tce.back();
+        // stash block: the fragment-layout stream of every InstanceNorm layer's frames (avc_long.hip lz_dec_so)
+        size_t st = 0;
+        for (int l = 0; l < nd; ++l) st += 2048 * (size_t)(cdiv(tdec[l], 16) + cdiv(tdec[l + 1], 16));
+        stash += st;
+        w.stash_per_utt = std::max(w.stash_per_utt, (int)st);   // (the longest's: non-zero = "stash" in dec_launch)
+        w.fl_ce += fz_fwd_flop(S->ce, tce, S->ce_bank_k);
+        w.fl_se2 += fz_fwd_flop(c, tse2, ctx->bank_k);
+        for (int bw = 0; bw < 2; ++bw) w.fl_dec[bw] += 2.0 * dec_mac(v, tdec, bw != 0);
+    }
+    if (dmalloc(w.rag_ce, B * sizeof(RagUtt)) || dmalloc(w.rag_se2, B * sizeof(RagUtt)) ||
+        dmalloc(w.rag_dec, B * sizeof(DecUtt)))
+        return 1;
+    HIPCHK(hipMemcpy(w.rag_ce.get(), rce.data(), B * sizeof(RagUtt), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(w.rag_se2.get(), rse2.data(), B * sizeof(RagUtt), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(w.rag_dec.get(), rdec.data(), B * sizeof(DecUtt), hipMemcpyHostToDevice));
+    const size_t Bz = B;
+    int rc = 0;
+    rc |= dalloc(w.src, w.S);
+    rc |= dalloc(w.mu, mu);
+    rc |= dalloc(w.lsig, mu);
+    for (DevBuf* b : {&w.emb, &w.pooled2, &w.gpooled2}) rc |= dalloc(*b, Bz * FZ_C);
+    rc |= dalloc(w.gemb, Bz * FZ_C * 4 * nd);
+    rc |= dalloc(w.hact, Bz * 2 * c.n_dense_blocks * FZ_C);
+    rc |= dalloc(w.cond, Bz * 2 * nd * 2 * FZ_C);
+    rc |= dalloc(w.gcond, Bz * 2 * nd * 2 * FZ_C);
+    rc |= dalloc(w.stash, stash);
+    rc |= dalloc(w.invstd, Bz * 2 * nd * FZ_C);
+    for (DevBuf* b : {&w.out, &w.tgt_out, &w.org_out, &w.gout, &w.gdec}) rc |= dalloc(*b, w.O);
+    if (rc || dmalloc(w.masks2, Bz * ws.mask_words * sizeof(unsigned long long))) return 1;
+    return alloc_long(w.lz, B, std::max(k.Ts, w.Tn), (int)ctx->bank_k.size() + 1 + 2 * c.n_conv_blocks);
+}
+
 static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws);
+static int ensure_vc_key(avc_ctx* ctx, const VcKey& k);
 
 // The VC workspace of a call (ctx->vc->cur) over the SpeakerEncoder workspace of (B, T): resolve the
 // key, look it up, build a new entry or re-plan one whose SpeakerEncoder workspace was re-planned, plan.
@@ -694,7 +782,32 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
     if (enc_lengths(S->ce, S->ce_bank_k, Ts, tce) || dec_lengths(S->cfg, tce.back(), tdec)) return 1;
     const int Tmax = std::max(Ts, tdec.back());
     const bool force = engine_for(ctx, Tmax) == AVC_ENGINE_LONG && Tmax <= 128;
-    const VcKey k{B, T, Ts, force || Ts > 128, force || tdec.back() > 128};
+    return ensure_vc_key(ctx, VcKey{B, T, Ts, force || Ts > 128, force || tdec.back() > 128, {}, {}});
+}
+
+// A ragged batch: utterance b attacks lens[b] frames with a source of src_lens[b] frames.  The SpeakerEncoder
+// workspace under it is the ragged one of `lens` on the long engine, whatever the lengths: every component of
+// the ragged VC path runs on the long engine, one launch per pass over the whole batch.
+static int ensure_vc_ws_ragged(avc_ctx* ctx, const std::vector<int>& lens, const std::vector<int>& src_lens,
+                               int n_iters) {
+    VcState* S = ctx->vc;
+    if (!S) return fail("no ContentEncoder/Decoder attached (avc_attach_vc)");
+    if (ctx->engine == AVC_ENGINE_LAYERED)
+        return fail("ragged e2e / fb / inference batches run on the long engine: not under AVC_ENGINE_LAYERED");
+    const int B = (int)lens.size();
+    if (B <= 0 || src_lens.size() != lens.size()) return fail("ragged batch: %zu source lengths for B=%d", src_lens.size(), B);
+    std::vector<int> a, b, c;   // the key's lengths are valid before anything is built or evicted for it
+    for (int u = 0; u < B; ++u)
+        if (ragged_src_lengths(ctx, u, src_lens[u], a, b, c)) return 1;
+    if (ensure_ws(ctx, B, 0, n_iters, &lens, true)) return 1;
+    return ensure_vc_key(ctx, VcKey{B, *std::max_element(lens.begin(), lens.end()),
+                                    *std::max_element(src_lens.begin(), src_lens.end()), true, true, lens, src_lens});
+}
+
+// look the key up over the SpeakerEncoder workspace of the call (ctx->cur), build / re-plan / plan
+static int ensure_vc_key(avc_ctx* ctx, const VcKey& k) {
+    VcState* S = ctx->vc;
+    Workspace& ws = *ctx->cur;
     S->cur = S->wss.find(k);
     if (S->cur && S->cur->ws_gen == ws.gen) {
         ++ctx->n_ws_hits;               // served by the cached workspace as it was (include/avc.h "hits")
@@ -712,7 +825,9 @@ static int ensure_vc_ws(avc_ctx* ctx, int B, int T, int Ts, int n_iters) {
         fail("hipStreamSynchronize failed");
         return drop_vc_cur(ctx);
     }
-    if ((fresh && build_vc_ws(ctx, *S->cur, k, ws)) || plan_vc_ws(ctx, *S->cur, ws)) return drop_vc_cur(ctx);
+    if ((fresh && (k.src_lens.empty() ? build_vc_ws(ctx, *S->cur, k, ws) : build_vc_ws_ragged(ctx, *S->cur, k, ws))) ||
+        plan_vc_ws(ctx, *S->cur, ws))
+        return drop_vc_cur(ctx);
     return 0;
 }
 
@@ -725,8 +840,9 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
     renew(w.pl);
     const int nbS = ctx->nb, nbC = (int)S->ce_bank_k.size();
     const int nd = v.dec_n_conv_blocks, M = 2 * nd * 2 * FZ_C;
-    const double se_fl = fz_fwd_flop(c, ws.Tl, ctx->bank_k) * B;
-    const double se2_fl = fz_fwd_flop(c, w.Tl_se2, ctx->bank_k) * B;
+    // (a ragged workspace: the sums over its utterances; every encoder pass takes its table of lengths)
+    const double se_fl = w.ragged ? ws.flop_fwd : fz_fwd_flop(c, ws.Tl, ctx->bank_k) * B;
+    const double se2_fl = w.ragged ? w.fl_se2 : fz_fwd_flop(c, w.Tl_se2, ctx->bank_k) * B;
     const int shS = enc_shape(c, nbS, T), shS2 = enc_shape(c, nbS, w.Tn);
     const int TNs = ws.Tl.back(), TNs2 = w.Tl_se2.back();
 
@@ -735,8 +851,9 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
         A.x = w.src.p;
         A.ce_mode = 1;
         A.mu_out = w.mu.p;
+        A.rag = w.rag_ce.get();
         w.pl.ce.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, enc_shape(S->ce, nbC, Ts), S->ce.kernel_size,
-                                           fz_fwd_flop(S->ce, w.Tl_ce, S->ce_bank_k) * B, "ce",
+                                           w.ragged ? w.fl_ce : fz_fwd_flop(S->ce, w.Tl_ce, S->ce_bank_k) * B, "ce",
                                            w.ce_long ? &w.lz.a : nullptr));
         w.pl.ce.launches.back().name = w.ce_long ? "lz_ce_fwd<f32>" : "ce_fwd_fused<f32>";
         // log_sigma = std_layer(h_N): the same pass with std_layer as the final 1x1 (on demand)
@@ -755,6 +872,7 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
         A.pooled = w.pooled2.p;
         A.masks = w.masks2.get();
         A.mask_words = ws.mask_words;
+        A.rag = w.rag_se2.get();
         w.pl.se2_pre.launches.push_back(enc_launch(L_FZ_FWD, PREC_F32, A, shS2, c.kernel_size, se2_fl, "se2",
                                                 w.se2_long ? &w.lz.a : nullptr));
         w.pl.se2_pre.launches.push_back(head_launch(ctx, B, TNs2, 0, w.pooled2.p, nullptr, ws.emb_fwd.p, nullptr, nullptr,
@@ -778,6 +896,7 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
                 A.mask_words = ws.mask_words;
                 A.write_masks = 1;
                 A.tick = ws.step.get();
+                A.rag = ws.rag.get();
                 Launch F = enc_launch(L_FZ_FWD, prec, A, shS, c.kernel_size, se_fl, "se", ws.lz ? &ws.lzs.a : nullptr);
                 Launch H = head_launch(ctx, B, TNs, 0, ws.pooled.p, nullptr, w.emb.p, nullptr, nullptr, nullptr,
                                        ws.step.get(), ws.scal.p, ws.iters_cap, prec);
@@ -816,6 +935,7 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
                 A.masks = w.masks2.get();
                 A.mask_words = ws.mask_words;
                 A.write_masks = 1;
+                A.rag = w.rag_se2.get();
                 Launch F2 = enc_launch(L_FZ_FWD, prec, A, shS2, c.kernel_size, se2_fl, "se2",
                                        w.se2_long ? &w.lz.a : nullptr);
                 Launch H2 = head_launch(ctx, B, TNs2, 1, w.pooled2.p, w.gpooled2.p, w.emb.p, ws.tgt.p, ws.org.p,
@@ -870,23 +990,24 @@ static int plan_vc_ws(avc_ctx* ctx, VcWs& w, Workspace& ws) {
     return 0;
 }
 
-// Decoder(ContentEncoder(src).mu, emb): emb [B][c_out] given (emb_dev) or SE(tgt) at Ts frames
+// Decoder(ContentEncoder(src).mu, emb): emb [B][c_out] given (emb_dev) or SE(tgt) at Ts frames.
+// src_lens (ragged batch, emb_dev only): src / out are packed blocks of src_lens[b] / Tn(src_lens[b]) frames.
 static int inference_impl(avc_ctx* ctx, const float* src, int Ts, const float* tgt, const float* emb_dev, int B,
-                          float* out, void* stream) {
+                          float* out, void* stream, const std::vector<int>* src_lens = nullptr) {
     if (!ctx || !src || !(tgt || emb_dev) || !out) return fail("avc_inference: null argument");
     hipStream_t us = (hipStream_t)stream;
-    if (ensure_vc_ws(ctx, B, Ts, Ts, 1)) return 1;
+    if (src_lens ? ensure_vc_ws_ragged(ctx, *src_lens, *src_lens, 1) : ensure_vc_ws(ctx, B, Ts, Ts, 1)) return 1;
     if (begin_call(ctx, us)) return 1;
     VcWs& w = *ctx->vc->cur;
     Workspace& ws = *ctx->cur;
-    if (d2d(ctx, w.src.p, src, (size_t)B * FZ_CIN * Ts) || run_plan(ctx, w.pl.ce, false)) return 1;
+    if (d2d(ctx, w.src.p, src, w.S) || run_plan(ctx, w.pl.ce, false)) return 1;
     if (tgt) {
         if (se_embed(ctx, tgt)) return 1;
     } else if (d2d(ctx, ws.emb_fwd.p, emb_dev, (size_t)B * ctx->cfg.c_out)) {
         return 1;
     }
     if (run_plan(ctx, w.pl.dec_pre, false)) return 1;
-    if (d2d(ctx, out, w.out.p, (size_t)B * DZ_COUT * w.Tn)) return 1;
+    if (d2d(ctx, out, w.out.p, w.O)) return 1;
     return end_call(ctx, us);
 }
 
@@ -901,32 +1022,44 @@ extern "C" int avc_inference_emb(avc_ctx* ctx, const float* src, int B, int T_sr
     return inference_impl(ctx, src, T_src, nullptr, emb, B, out, stream);
 }
 
+// A ragged batch: src is packed [80][src_lengths[b]] blocks in batch order (host array of lengths), emb
+// [B][c_out], out packed [80][Tn(src_lengths[b])] blocks.  One launch per component over every length.
+extern "C" int avc_inference_ragged(avc_ctx* ctx, const float* src, const int* src_lengths, int B, const float* emb,
+                                    float* out, void* stream) {
+    if (!ctx || !src_lengths || !emb) return fail("avc_inference_ragged: null argument");
+    if (B <= 0) return fail("avc_inference_ragged: batch size must be positive (got %d)", B);
+    const std::vector<int> sl(src_lengths, src_lengths + B);
+    return inference_impl(ctx, src, 0, nullptr, emb, B, out, stream, &sl);
+}
+
 // e2e / fb attack; vc_src has Ts frames, vc_tgt / ptb0 T frames; the target embedding is
-// SE(adv_tgt) at T frames (adv_tgt given) or the caller's tgt_emb [B][c_out]
+// SE(adv_tgt) at T frames (adv_tgt given) or the caller's tgt_emb [B][c_out].
+// lens / src_lens (ragged batch, tgt_emb only): every array is packed blocks of the utterances' own lengths.
 static int vc_attack(avc_ctx* ctx, int kind, const float* vc_src, int Ts, const float* vc_tgt, const float* adv_tgt,
                      const float* tgt_emb, const float* ptb0, int B, int T, float eps, int n_iters, float* out_adv,
-                     const avc_attack_opts* opts, void* stream) {
+                     const avc_attack_opts* opts, void* stream, const std::vector<int>* lens = nullptr,
+                     const std::vector<int>* src_lens = nullptr) {
     const char* nm = kind == 0 ? "avc_e2e_attack" : "avc_fb_attack";
     if (!ctx || !vc_src || !vc_tgt || !(adv_tgt || tgt_emb) || !ptb0 || !out_adv) return fail("%s: null argument", nm);
     if (n_iters < 0) return fail("n_iters must be >= 0");
     avc_attack_opts o;
     if (attack_opts(opts, &o)) return 1;
     hipStream_t us = (hipStream_t)stream;
-    if (ensure_vc_ws(ctx, B, T, Ts, n_iters)) return 1;
+    if (lens ? ensure_vc_ws_ragged(ctx, *lens, *src_lens, n_iters) : ensure_vc_ws(ctx, B, T, Ts, n_iters)) return 1;
     Workspace& ws = *ctx->cur;
     VcWs& w = *ctx->vc->cur;
     const int prec = o.precision == AVC_PREC_BF16 ? PREC_BF16 : PREC_F32;
     if (begin_call(ctx, us)) return 1;
     const avc_se_cfg& c = ctx->cfg;
-    const size_t X = (size_t)B * c.c_in * T;
     const bool mean = o.reduction == AVC_REDUCE_MEAN;
     const float g_emb = (float)(2.0 / ((mean ? (double)B : 1.0) * c.c_out));
+    // (a ragged batch: every utterance's own 2 / (80 Tn_b), in the Decoder's table)
     const float g_out = (float)(2.0 / ((mean ? (double)B : 1.0) * DZ_COUT * w.Tn));
     if (stage_attack_consts(ctx, n_iters, eps, g_emb, g_out, o)) return 1;
 
-    if (d2d(ctx, ws.vc.p, vc_tgt, X) || d2d(ctx, w.src.p, vc_src, (size_t)B * c.c_in * Ts)) return 1;
+    if (d2d(ctx, ws.vc.p, vc_tgt, ws.X) || d2d(ctx, w.src.p, vc_src, w.S)) return 1;
     if (run_plan(ctx, w.pl.ce, false)) return 1;                                  // mu = CE(vc_src)
-    const size_t O = (size_t)B * DZ_COUT * w.Tn, Eb = (size_t)B * c.c_out;
+    const size_t O = w.O, Eb = (size_t)B * c.c_out;
     if (kind == 0) {
         // org_out = inference(vc_src, vc_tgt), tgt_out = inference(vc_src, adv_tgt)  (attack_utils.py:35-37)
         if (se_embed(ctx, vc_tgt) || run_plan(ctx, w.pl.dec_pre, false) || d2d(ctx, w.org_out.p, w.out.p, O)) return 1;
@@ -971,6 +1104,37 @@ extern "C" int avc_fb_attack_emb(avc_ctx* ctx, const float* vc_src, int T_src, c
                                  float* out_adv, const avc_attack_opts* opts, void* stream) {
     if (!tgt_emb) return fail("avc_fb_attack_emb: null argument");
     return vc_attack(ctx, 1, vc_src, T_src, vc_tgt, nullptr, tgt_emb, ptb0, B, T, eps, n_iters, out_adv, opts, stream);
+}
+
+// Ragged batches: utterance b has src_lengths[b] source and lengths[b] attacked frames (host arrays); vc_src is
+// packed [80][src_lengths[b]] blocks, vc_tgt / ptb0 / out_adv (and opts->grad0) packed [80][lengths[b]] blocks in
+// batch order, tgt_emb [B][c_out] = SE(adv_tgt_b) at adv_tgt_b's own length.  Every pass of every component is
+// one launch over the whole batch on the long engine.
+static int vc_attack_ragged(avc_ctx* ctx, int kind, const float* vc_src, const int* src_lengths, const float* vc_tgt,
+                            const int* lengths, int B, const float* tgt_emb, const float* ptb0, float eps, int n_iters,
+                            float* out_adv, const avc_attack_opts* opts, void* stream) {
+    const char* nm = kind == 0 ? "avc_e2e_attack_ragged" : "avc_fb_attack_ragged";
+    if (!ctx || !src_lengths || !lengths || !tgt_emb) return fail("%s: null argument", nm);
+    if (B <= 0) return fail("%s: batch size must be positive (got %d)", nm, B);
+    if (opts && opts->reduction != AVC_REDUCE_INDEPENDENT)
+        return fail("%s: only independent per-utterance attacks (reduction 0)", nm);
+    const std::vector<int> lens(lengths, lengths + B), sl(src_lengths, src_lengths + B);
+    return vc_attack(ctx, kind, vc_src, 0, vc_tgt, nullptr, tgt_emb, ptb0, B, 0, eps, n_iters, out_adv, opts, stream,
+                     &lens, &sl);
+}
+
+extern "C" int avc_e2e_attack_ragged(avc_ctx* ctx, const float* vc_src, const int* src_lengths, const float* vc_tgt,
+                                     const int* lengths, int B, const float* tgt_emb, const float* ptb0, float eps,
+                                     int n_iters, float* out_adv, const avc_attack_opts* opts, void* stream) {
+    return vc_attack_ragged(ctx, 0, vc_src, src_lengths, vc_tgt, lengths, B, tgt_emb, ptb0, eps, n_iters, out_adv, opts,
+                            stream);
+}
+
+extern "C" int avc_fb_attack_ragged(avc_ctx* ctx, const float* vc_src, const int* src_lengths, const float* vc_tgt,
+                                    const int* lengths, int B, const float* tgt_emb, const float* ptb0, float eps,
+                                    int n_iters, float* out_adv, const avc_attack_opts* opts, void* stream) {
+    return vc_attack_ragged(ctx, 1, vc_src, src_lengths, vc_tgt, lengths, B, tgt_emb, ptb0, eps, n_iters, out_adv, opts,
+                            stream);
 }
 
 // ContentEncoder.forward (models.py:181-210): (mu, log_sigma) [B][c_out][Tce] of x [B][80][T], fp32

@@ -237,6 +237,35 @@ int avc_fb_attack_emb(avc_ctx* ctx, const float* vc_src, int T_src, const float*
                       const float* tgt_emb, const float* ptb0, int B, int T, float eps, int n_iters,
                       float* out_adv, const avc_attack_opts* opts, void* stream);
 
+/* e2e / feedback attacks and inference on a RAGGED batch: utterance b has src_lengths[b] source frames and
+ * lengths[b] attacked frames (HOST int arrays of B), as real utterances do (attack.py:41-56 loads vc_src,
+ * vc_tgt and adv_tgt from three wavs of three lengths; every length has its own reflect padding, ceil-mode
+ * pooling, InstanceNorm statistics and output MSE mean).  Device fp32, blocks in batch order:
+ *   vc_src                              packed [80][src_lengths[b]]
+ *   vc_tgt, ptb0, out_adv, opts->grad0  packed [80][lengths[b]]
+ *   out (avc_inference_ragged)          packed [80][Tn_b], Tn_b = avc_vc_out_frames(src_lengths[b])
+ *   tgt_emb / emb                       [B, c_out] = SpeakerEncoder(adv_tgt_b), each adv_tgt embedded at its
+ *                                       own length (avc_se_forward)
+ *   opts->losses                        [n_iters][B]
+ * Engine rule: every component -- ContentEncoder, Decoder, SpeakerEncoder(adv) and, for fb, SpeakerEncoder(decoder
+ * output) -- runs on the long engine whatever the lengths, ONE launch per pass over the whole batch with
+ * per-workgroup lengths and packed offsets; the calls fail under AVC_ENGINE_LAYERED.  Utterance b's result
+ * equals its own avc_*_attack_emb / avc_inference_emb under AVC_ENGINE_LONG bit for bit (the e2e loss mean and
+ * gradient scale are per utterance, n = 80 Tn_b).  A spectral-norm Decoder takes one power iteration per Decoder
+ * forward over the batch, as an equal-length batch does.  opts->reduction must be INDEPENDENT; AVC_UPDATE_PGD
+ * passes through.  The workspace is cached by both length vectors: a second call over the same lengths builds,
+ * re-plans and captures nothing (avc_ws_stats).
+ * Replace B calls of AdaInVC.inference (models.py:472-489), attack_utils.e2e_attack (attack_utils.py:7-48) and
+ * attack_utils.fb_attack (attack_utils.py:89-130), one per utterance. */
+int avc_inference_ragged(avc_ctx* ctx, const float* src, const int* src_lengths, int B, const float* emb,
+                         float* out, void* stream);
+int avc_e2e_attack_ragged(avc_ctx* ctx, const float* vc_src, const int* src_lengths, const float* vc_tgt,
+                          const int* lengths, int B, const float* tgt_emb, const float* ptb0, float eps,
+                          int n_iters, float* out_adv, const avc_attack_opts* opts, void* stream);
+int avc_fb_attack_ragged(avc_ctx* ctx, const float* vc_src, const int* src_lengths, const float* vc_tgt,
+                         const int* lengths, int B, const float* tgt_emb, const float* ptb0, float eps,
+                         int n_iters, float* out_adv, const avc_attack_opts* opts, void* stream);
+
 /* ---- VSMask PredictiveModel forward (models/predictive_model.py:53-110, BASELINE config 5) ----
  * Eval-mode inference (BatchNorm running statistics).  `weights` = HOST fp32 floating
  * tensors of PredictiveModel.state_dict() in order (num_batches_tracked excluded). */
